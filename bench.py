@@ -11,13 +11,27 @@ overlapped with backward + BN-buffer broadcast), fused SGD update.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --profile            # the same run under rocprofv3 --kernel-trace --stats
+    python bench.py --full               # the headline run plus the side measurements and checks
+    python bench.py --dump-outputs DIR   # also write the last timed step's results as DIR/<name>.npy
 
-``--gpus N`` without torchrun starts N local ranks itself (parallel/spawn.py: fresh child
-processes, the parent never touches the GPU).  For N > 1, rank 0 first times the same step alone
-(``--solo-steps``, no communicator; the other ranks wait) so the JSON line carries a same-run
-scaling efficiency; after the timed steps a short diagnostic phase records the communication left
-exposed after backward and each bucket's collective time with timing events (kept out of the
-timed region), and the parameter arenas are compared across ranks.
+A plain run does only what the headline figure needs: set up, warm up, time ``--steps`` steps,
+print one JSON line (``ms_per_step``: milliseconds per timed step).  ``--gpus N`` without torchrun
+starts N local ranks itself (parallel/spawn.py: fresh child processes, the parent never touches
+the GPU).  For N > 1 the warmup still picks the gradient-sync plan the timed steps then run
+(``--comm-tune``): that choice is part of the headline figure.
+
+``--full`` adds everything else the bench can measure or check.  For N > 1, rank 0 first times the
+same step alone (``--solo-steps``, no communicator; the other ranks wait) so the JSON line carries
+a same-run scaling efficiency; after the timed steps a short diagnostic phase (``--diag-steps``)
+records the communication left exposed after backward and each bucket's collective time with
+timing events (kept out of the timed region), and the parameter arenas are compared across ranks
+(``replicas_identical``).  Without ``--full`` those fields of the JSON line are null.
+
+``--dump-outputs DIR``: right after the timed steps rank 0 writes what the last timed step left
+its caller -- the loss, the gradient arena, and the updated parameter, momentum and BN-buffer
+arenas -- as float32 ``DIR/<name>.npy`` (an arena above ``DUMP_CAP`` elements as a fixed, seeded
+sample of it).  Data, sampling, augmentation and initialisation are all seeded, so the same
+arguments give the same inputs in every run and two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -69,11 +83,18 @@ def parse(argv=None):
                          "operands, 3 products; default) | x3 = fp32-grade from bf16 matrix cores (3 planes, "
                          "6 products) | fp32 = fp32 MFMA | bf16 = mixed precision.  h2 and x3 are pinned "
                          "against fp64 at this exact config by tests/test_parity256_gpu.py")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline run: the same-run 1-GPU figure (--solo-steps), the diagnostic steps "
+                         "(--diag-steps) and the cross-rank replica check; off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's loss, gradients and updated parameters, "
+                         "momentum and BN buffers as float32 DIR/<name>.npy (rank 0)")
     ap.add_argument("--solo-steps", type=int, default=None,
-                    help="N>1: steps rank 0 times alone first (same-run 1-GPU figure; 0 = skip; default "
+                    help="--full, N>1: steps rank 0 times alone first (same-run 1-GPU figure; 0 = skip; default "
                          "min(steps, 30))")
     ap.add_argument("--diag-steps", type=int, default=5,
-                    help="diagnostic steps after the timed region (exposed comm / per-bucket times; 0 = off)")
+                    help="--full: diagnostic steps after the timed region (exposed comm / per-bucket times; "
+                         "0 = off)")
     ap.add_argument("--comm-tune", default="auto", choices=["auto", "off"],
                     help="N>1, ddp/allreduce modes: in the warmup, time a few gradient-sync plans (bucket size, "
                          "tail bucket, per-bucket update inside backward) on the real fabric and keep the fastest "
@@ -422,6 +443,27 @@ def solo_phase(a, dev, steps, warmup):
     return a.batch * steps / el
 
 
+DUMP_CAP = 1 << 22  # elements per dumped array (16 MB of float32): five arrays stay under 64 MB
+
+
+@torch.no_grad()
+def dump_outputs(path, engine):
+    """``--dump-outputs``: what the step just taken left its caller, one float32 .npy per array.
+    An arena above DUMP_CAP elements is written as a sample of it: DUMP_CAP sorted positions drawn
+    once from a CPU generator with seed 0, so every run and every build samples the same ones."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    outs = {"loss": engine.loss, "grads": engine.grads.flat, "params": engine.params.flat,
+            "momentum": engine.mom.flat, "bn_buffers": engine.buffers.flat}
+    for name, t in outs.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_CAP:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_CAP].sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     a = parse(argv)
@@ -443,7 +485,7 @@ def main(argv=None):
 
     solo_img_s = None
     solo_steps = min(a.steps, 30) if a.solo_steps is None else a.solo_steps
-    if ctx.world > 1 and solo_steps > 0:
+    if a.full and ctx.world > 1 and solo_steps > 0:
         if ctx.rank == 0:
             solo_img_s = solo_phase(a, dev, solo_steps, min(a.warmup, 5))
         ctx.barrier()
@@ -461,10 +503,12 @@ def main(argv=None):
     loss = float(engine.loss.item())
     ms = el / a.steps * 1e3
     img_s = a.batch * ctx.world * a.steps / el
+    if a.dump_outputs and ctx.rank == 0:  # (before any further step: the last timed step's results)
+        dump_outputs(a.dump_outputs, engine)
 
     diag = None
-    live = [] if isinstance(ctx.comm, IpcComm) else None
-    if a.diag_steps > 0 and dev.type == "cuda":
+    live = [] if a.full and isinstance(ctx.comm, IpcComm) else None
+    if a.full and a.diag_steps > 0 and dev.type == "cuda":
         probe = EventProbe(dev)
         sync.probe = probe
         step = make_step(engine, sync, it, probe=probe)
@@ -482,7 +526,7 @@ def main(argv=None):
         diag = step_comm_report(samples, len(sync.buckets))
         diag["exposed_comm_ms"] = ctx.all_max(diag["exposed_comm_ms"] or 0.0)
     benchlib.device_barrier(ctx, dev)
-    pdiff = benchlib.replicas_max_diff(ctx.comm, engine.params.flat)
+    pdiff = benchlib.replicas_max_diff(ctx.comm, engine.params.flat) if a.full else None
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     cw = benchlib.comm_world(ctx.comm)
@@ -531,7 +575,8 @@ def main(argv=None):
             "ipc_live_check": (None if live is None else
                                {"checks": len(live), "ok": all(c["ok"] for c in live),
                                 "max_rel_err": max((c["rel_err"] for c in live), default=None)}),
-            "replicas_identical": pdiff == 0.0,
+            # (--full; None: the replicas were not compared)
+            "replicas_identical": pdiff == 0.0 if pdiff is not None else None,
             "replica_param_max_diff": pdiff,
             "comm_diag": diag,
             # same-run stock-torch comparison (only with --torch-baseline; None otherwise)

@@ -83,7 +83,7 @@ def test_bench_self_launch_two_ranks_cpu():
     """``bench.py --gpus 2`` with no launcher environment: 2 gloo ranks on CPU through the same
     spawn path the driver's 8-GPU run takes; one JSON line with the scaling fields."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", spawn.SPAWNED_ENV)}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "cpu",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--device", "cpu",
                         "--batch", "4", "--steps", "2", "--warmup", "1", "--solo-steps", "1",
                         "--comm-tune-steps", "1", "--comm-tune-budget", "500"],  # (a loaded CPU: every plan timed)
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
@@ -131,6 +131,46 @@ def test_bench_single_rank_reports_no_rccl_world():
     assert rec["n_gpus"] == 1 and rec["config"]["comm"] == "null"
     assert rec["rccl_world"] is None
     assert rec["vs_torch_eager_fp32"] is None and rec["torch_eager_fp32_img_s"] is None
+
+
+def _plain_dump(out):
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", spawn.SPAWNED_ENV)}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--device", "cpu", "--batch",
+                        "4", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times its steps and nothing else: the side measurements' fields are
+    null.  --dump-outputs writes the last timed step's loss, gradients, parameters, momentum and BN
+    buffers as float32 .npy (arenas above DUMP_CAP elements as the seeded sample), under 64 MB in
+    all; the inputs are seeded, so a second run with the same arguments writes the same arrays."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rec = _plain_dump(tmp_path / "a")
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    # images/sec = batch / step time; the line rounds the value to 0.1 and ms_per_step to 1e-4
+    assert rec["value"] == pytest.approx(4 * 1e3 / rec["ms_per_step"], abs=0.051, rel=1e-4)
+    for k in ("comm_diag", "solo_img_s", "scaling_efficiency", "replicas_identical", "replica_param_max_diff"):
+        assert rec[k] is None, k
+    names = ["bn_buffers", "grads", "loss", "momentum", "params"]
+    assert sorted(os.listdir(tmp_path / "a")) == [n + ".npy" for n in names]
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(v.dtype == np.float32 and v.ndim == 1 and np.isfinite(v).all() for v in a.values())
+    assert sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in names) <= 64 * 2 ** 20
+    assert a["loss"].size == 1 and a["loss"][0] == pytest.approx(rec["final_loss"], abs=1e-4)  # (rounded to 4 places)
+    assert a["params"].size == a["grads"].size == a["momentum"].size == bench.DUMP_CAP  # VGG-11: 9.2 M parameters
+    assert np.abs(a["grads"]).max() > 0 and np.abs(a["momentum"]).max() > 0
+    _plain_dump(tmp_path / "b")
+    for n in names:
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / (n + ".npy"))), n
 
 
 def test_comm_world_only_for_rccl():
@@ -336,8 +376,8 @@ def test_ipc_collective_pieces_cover_the_tensor():
 def _bench8(extra_env, args):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", spawn.SPAWNED_ENV)}
     env.update(OMP_NUM_THREADS="1", **extra_env)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--device", "cpu", "--batch", "2",
-                        "--steps", "1", "--warmup", "1", "--solo-steps", "0", "--diag-steps", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--device", "cpu",
+                        "--batch", "2", "--steps", "1", "--warmup", "1", "--solo-steps", "0", "--diag-steps", "0",
                         "--comm-tune-steps", "1"] + args, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -36,7 +36,7 @@ def _agree(sums):
 
 
 def _run(mode):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--comm", "gloo", "--mode", mode,
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--comm", "gloo", "--mode", mode,
            "--steps", "3", "--warmup", "2", "--solo-steps", "0", "--diag-steps", "1", "--launch-timeout", "100"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **SERIAL)
     env.pop("WORLD_SIZE", None)
@@ -72,8 +72,8 @@ def test_modes_agree(runs):
 
 def test_four_ranks_ddp_share_one_gpu():
     """W = 4 (bucket all-reduce of four contributions, 1/W folded into the update)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--comm", "gloo", "--mode", "ddp",
-           "--steps", "2", "--warmup", "1", "--solo-steps", "0", "--diag-steps", "0", "--batch", "64",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--comm", "gloo", "--mode",
+           "ddp", "--steps", "2", "--warmup", "1", "--solo-steps", "0", "--diag-steps", "0", "--batch", "64",
            "--launch-timeout", "100"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
@@ -101,8 +101,8 @@ def test_torchrun_launch_two_ranks():
     from distributed_pytorch_amd.parallel.spawn import free_port
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--comm",
-           "gloo", "--steps", "3", "--warmup", "1", "--solo-steps", "2", "--diag-steps", "1"]
+           "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2",
+           "--comm", "gloo", "--steps", "3", "--warmup", "1", "--solo-steps", "2", "--diag-steps", "1"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DPA_STORE_PORT"):
         env.pop(k, None)
@@ -160,7 +160,8 @@ def test_ipc_collectives_ranks_share_one_gpu(world, stage, inbox):
 
 
 def _bench(args, script="bench.py", timeout=110, env_extra=None):
-    cmd = [sys.executable, os.path.join(ROOT, script)] + args + ["--launch-timeout", str(timeout - 10)]
+    full = ["--full"] if script == "bench.py" else []  # (the replica check and the diagnostic steps)
+    cmd = [sys.executable, os.path.join(ROOT, script)] + full + args + ["--launch-timeout", str(timeout - 10)]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **(env_extra or {}))
     env.pop("WORLD_SIZE", None)
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
