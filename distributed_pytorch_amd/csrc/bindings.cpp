@@ -11,6 +11,15 @@
 extern "C" {
 int dpa_sgd_flat(float* p, const float* g, float* buf, long n, float lr, float momentum, float wd, float gscale,
                  int first, unsigned short* planes, long ps, int np, hipStream_t s);
+int dpa_opt_chunk();
+int dpa_opt_max_segments();
+int dpa_sqnorm_partials(const float* p, const float* g, const long* bmap, long nblocks, long n, int nseg,
+                        double* partials, hipStream_t s);
+int dpa_lars_finalize(const double* partials, long nblocks, const long* segs, int nseg, float* table, double* stats,
+                      double gs, double max_norm, double trust, double wd, double eps, hipStream_t s);
+int dpa_sgd_segmented(float* p, const float* g, float* buf, const long* bmap, long nblocks, long n, int nseg,
+                      const float* table, float lr, float momentum, float wd, int first, unsigned short* planes,
+                      long ps, int np, hipStream_t s);
 int dpa_spin(long long usec, int* done, hipStream_t s);
 int dpa_mean_of_w(const float* in, float* out, long n, int W, hipStream_t s);
 int dpa_add_inplace(void* out, const void* add, long n, int bf, hipStream_t s);
@@ -75,6 +84,7 @@ int dpa_h2_ovf_conv(int clear);
 int dpa_h2_ovf_bn(int clear);
 int dpa_h2_ovf_sgd(int clear);
 int dpa_h2_ovf_fused(int clear);
+int dpa_h2_ovf_lars(int clear);
 int dpa_pad_split8(const float* x, unsigned short* out, long npix, int cin, long ps, int np, hipStream_t st);
 int dpa_conv_x3_dgrad(const unsigned short* dz, long dzps, const unsigned short* w, long wps, void* dx, float* slab,
                       int N, int Hd, int Wd, int K, int C, int R, int S, int stride, int pad, int H, int W, int splits,
@@ -99,6 +109,7 @@ int* dpa_h2_ovf_conv_addr();
 int* dpa_h2_ovf_bn_addr();
 int* dpa_h2_ovf_sgd_addr();
 int* dpa_h2_ovf_fused_addr();
+int* dpa_h2_ovf_lars_addr();
 int dpa_bn_apply_wide(const unsigned short* z, const unsigned short* res, unsigned short* out, unsigned char* mask,
                       const float* scale, const float* shift, long M, int C, int act, hipStream_t st,
                       const float* rscale, const float* rshift);
@@ -188,6 +199,81 @@ void sgd_flat(Tensor p, Tensor g, Tensor buf, double lr, double momentum, double
       "sgd_flat");
 }
 
+// ---- LARS / global-norm clipping over the arenas (kernels/lars.hip) ----
+// bmap: int64 [nblocks, 3] (segment, start, length) per chunk; segs: int64 [nseg, 3] (first chunk,
+// chunks, adapted) per segment.  Both are device tables the host built once (utils/arena.block_map),
+// so their shapes are checked here and every entry against the arena by the kernel that reads it
+// (an entry outside the arena is skipped): a host check would need a device round trip per step.
+const long* opt_table(const Tensor& t, const char* name) {
+  need(t, name, at::kLong);
+  TORCH_CHECK(t.dim() == 2 && t.size(1) == 3, name, " must be int64 [n, 3]");
+  return reinterpret_cast<const long*>(t.data_ptr<int64_t>());
+}
+
+void opt_arenas(const Tensor& p, const Tensor& g, const char* what) {
+  need(p, "p");
+  need(g, "g");
+  TORCH_CHECK(p.numel() == g.numel() && p.numel() % 64 == 0, what, ": p and g must have one size, a multiple of 64");
+}
+
+// partials: float64 [nblocks, 2] = (sum p^2, sum g^2) of every chunk
+void sqnorm_partials(Tensor p, Tensor g, Tensor bmap, Tensor partials, int64_t nseg) {
+  opt_arenas(p, g, "sqnorm_partials");
+  const long* bm = opt_table(bmap, "bmap");
+  need(partials, "partials", at::kDouble);
+  TORCH_CHECK(partials.numel() == 2 * bmap.size(0), "sqnorm_partials: partials must be float64 [nblocks, 2]");
+  TORCH_CHECK(nseg >= 1 && nseg <= dpa_opt_max_segments(), "sqnorm_partials: segment count out of range");
+  chk(dpa_sqnorm_partials(fp(p), fp(g), bm, bmap.size(0), p.numel(), (int)nseg, partials.data_ptr<double>(),
+                          cur_stream()),
+      "sqnorm_partials");
+}
+
+// table: float32 [nseg + 1] (trust ratio per segment, then the gradient multiplier gs * clip);
+// stats: float64 [2 nseg + 2] (|p| per segment, |gs g| per segment, |gs g| of the arena, clip)
+void lars_finalize(Tensor partials, Tensor segs, Tensor table, Tensor stats, double gscale, double max_norm,
+                   double trust_coef, double wd, double eps) {
+  need(partials, "partials", at::kDouble);
+  const long* sg = opt_table(segs, "segs");
+  need(table, "table");
+  need(stats, "stats", at::kDouble);
+  const int64_t nseg = segs.size(0);
+  TORCH_CHECK(nseg >= 1 && nseg <= dpa_opt_max_segments(), "lars_finalize: at most ", dpa_opt_max_segments(),
+              " segments");
+  TORCH_CHECK(partials.numel() % 2 == 0 && table.numel() == nseg + 1 && stats.numel() == 2 * nseg + 2,
+              "lars_finalize: sizes (partials [nblocks, 2], table [nseg + 1], stats [2 nseg + 2])");
+  chk(dpa_lars_finalize(partials.data_ptr<double>(), partials.numel() / 2, sg, (int)nseg, fp(table),
+                        stats.data_ptr<double>(), gscale, max_norm, trust_coef, wd, eps, cur_stream()),
+      "lars_finalize");
+}
+
+// the update of sgd_flat over the whole arena, chunk by chunk, with table's ratios and multiplier
+void sgd_segmented(Tensor p, Tensor g, Tensor buf, Tensor bmap, Tensor table, double lr, double momentum, double wd,
+                   bool first, OptT planes) {
+  opt_arenas(p, g, "sgd_segmented");
+  need(buf, "buf");
+  TORCH_CHECK(buf.numel() == p.numel(), "sgd_segmented sizes");
+  const long* bm = opt_table(bmap, "bmap");
+  need(table, "table");
+  const int64_t nseg = table.numel() - 1;
+  TORCH_CHECK(nseg >= 1 && nseg <= dpa_opt_max_segments(), "sgd_segmented: table must be float32 [nseg + 1]");
+  unsigned short* pl = nullptr;
+  long ps = 0;
+  int np = 0;
+  if (planes.has_value() && planes->defined()) {
+    const Tensor& t = *planes;
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 2 && t.size(1) == p.numel() &&
+                    ((t.scalar_type() == at::kBFloat16 && (t.size(0) == 1 || t.size(0) == 3)) ||
+                     (t.scalar_type() == at::kHalf && t.size(0) == 2)),
+                "sgd_segmented: planes must be contiguous bfloat16 [1 or 3, p.numel()] or float16 [2, p.numel()]");
+    np = t.size(0);
+    ps = t.stride(0);
+    pl = reinterpret_cast<unsigned short*>(t.data_ptr());
+  }
+  chk(dpa_sgd_segmented(fp(p), fp(g), fp(buf), bm, bmap.size(0), p.numel(), (int)nseg, fp(table), (float)lr,
+                        (float)momentum, (float)wd, first ? 1 : 0, pl, ps, np, cur_stream()),
+      "sgd_segmented");
+}
+
 // Diagnostics: occupy the current stream for ~usec microseconds (one wave, bounded loop) and then
 // write 1 to done[0].  Used to hold a collective behind a long kernel (watchdog timeout test).
 // one int32 word on the GPU (a stream-signal flag or timeout word)
@@ -215,7 +301,8 @@ void set_signal(Tensor sig, int64_t val) {
 // device addresses of the fp16-pair overflow words of every kernel file (per-step health snapshot)
 std::vector<int64_t> h2_overflow_addrs() {
   std::vector<int64_t> out;
-  for (int* (*f)() : {dpa_h2_ovf_conv_addr, dpa_h2_ovf_bn_addr, dpa_h2_ovf_sgd_addr, dpa_h2_ovf_fused_addr}) {
+  for (int* (*f)() : {dpa_h2_ovf_conv_addr, dpa_h2_ovf_bn_addr, dpa_h2_ovf_sgd_addr, dpa_h2_ovf_fused_addr,
+                       dpa_h2_ovf_lars_addr}) {
     int* p = f();
     TORCH_CHECK(p != nullptr, "h2_overflow_addrs: hipGetSymbolAddress failed");
     out.push_back(reinterpret_cast<int64_t>(p));
@@ -518,7 +605,7 @@ void split_planes(Tensor x, Tensor out, double scale) {
 // clear: reset them
 bool h2_overflow(bool clear) {
   int any = 0;
-  for (int (*f)(int) : {dpa_h2_ovf_conv, dpa_h2_ovf_bn, dpa_h2_ovf_sgd, dpa_h2_ovf_fused}) {
+  for (int (*f)(int) : {dpa_h2_ovf_conv, dpa_h2_ovf_bn, dpa_h2_ovf_sgd, dpa_h2_ovf_fused, dpa_h2_ovf_lars}) {
     const int v = f(clear ? 1 : 0);
     TORCH_CHECK(v >= 0, "h2_overflow: could not read an overflow word");
     any |= v;
@@ -1193,6 +1280,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("sgd_flat", &sgd_flat, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("lr"), py::arg("momentum"),
         py::arg("wd"), py::arg("gscale"), py::arg("first"), py::arg("offset") = 0, py::arg("count") = -1,
         py::arg("planes") = py::none());
+  m.def("sqnorm_partials", &sqnorm_partials, py::arg("p"), py::arg("g"), py::arg("bmap"), py::arg("partials"),
+        py::arg("nseg"));
+  m.def("lars_finalize", &lars_finalize, py::arg("partials"), py::arg("segs"), py::arg("table"), py::arg("stats"),
+        py::arg("gscale"), py::arg("max_norm"), py::arg("trust_coef"), py::arg("wd"), py::arg("eps"));
+  m.def("sgd_segmented", &sgd_segmented, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("bmap"),
+        py::arg("table"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("first"),
+        py::arg("planes") = py::none());
+  m.attr("OPT_CHUNK") = (int64_t)dpa_opt_chunk();  // chunk length of the block map (kernels/lars.hip)
   m.def("spin", &spin, py::arg("usec"), py::arg("done"));
   m.def("mean_of_w", &mean_of_w);
   m.def("add_inplace", &add_inplace);

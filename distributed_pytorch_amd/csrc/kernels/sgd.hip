@@ -5,7 +5,9 @@
 //
 // torch semantics (dampening 0, nesterov False):
 //   d = g*scale + wd*p ; buf = first ? d : momentum*buf + d ; p -= lr*buf
+// (the per-element code is sgd_update.h, shared with the LARS / clipping update of lars.hip)
 #include "common.h"
+#include "sgd_update.h"
 
 // NP > 0: the updated parameters are also written as NP bf16 operand planes (plane stride ps, same
 // element index as the arena): the conv kernels' weight operands are refreshed in the same pass
@@ -17,39 +19,7 @@ __global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ p, co
                                                        long ps) {
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 pv = reinterpret_cast<float4*>(p)[i];
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    float4 bv;
-    float d0 = gv.x * gscale + wd * pv.x;
-    float d1 = gv.y * gscale + wd * pv.y;
-    float d2 = gv.z * gscale + wd * pv.z;
-    float d3 = gv.w * gscale + wd * pv.w;
-    if (first) {
-      bv = make_float4(d0, d1, d2, d3);
-    } else {
-      bv = reinterpret_cast<float4*>(buf)[i];
-      bv.x = momentum * bv.x + d0;
-      bv.y = momentum * bv.y + d1;
-      bv.z = momentum * bv.z + d2;
-      bv.w = momentum * bv.w + d3;
-    }
-    pv.x -= lr * bv.x;
-    pv.y -= lr * bv.y;
-    pv.z -= lr * bv.z;
-    pv.w -= lr * bv.w;
-    reinterpret_cast<float4*>(buf)[i] = bv;
-    reinterpret_cast<float4*>(p)[i] = pv;
-    if constexpr (NP > 0) {
-      u16 o[4][3];
-      constexpr float s = NP == 2 ? H2_SW : 1.f;  // fp16 pairs: the weight planes' scale
-      split_val<NP>(pv.x, o[0], s);
-      split_val<NP>(pv.y, o[1], s);
-      split_val<NP>(pv.z, o[2], s);
-      split_val<NP>(pv.w, o[3], s);
-#pragma unroll
-      for (int q = 0; q < NP; ++q)
-        reinterpret_cast<ushort4*>(planes + q * ps)[i] = make_ushort4(o[0][q], o[1][q], o[2][q], o[3][q]);
-    }
+    sgd_update4<NP>(p, g, buf, i, lr, momentum, wd, gscale, 1.f, first, planes, ps);
   }
 }
 

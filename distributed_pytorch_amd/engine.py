@@ -13,7 +13,8 @@ step is a static schedule of native kernels over persistent buffers:
             with flipped taps; its split-K slabs are summed inside the next bn_bwd)
   split-K   forward/dgrad partial slabs are never reduced by a separate pass: bn_fwd_stats /
             bn_bwd sum them while computing their statistics
-  update    sgd_flat over the flat parameter/grad/momentum arenas (one launch)
+  update    sgd_flat over the flat parameter/grad/momentum arenas (one launch); with LARS or
+            gradient clipping: sqnorm_partials → lars_finalize → sgd_segmented (three launches)
 
 Parameters/grads/momentum are three :class:`~distributed_pytorch_amd.utils.arena.Arena` s with
 identical layout (reference ``named_parameters()`` order; conv weights stored KRSC, the first
@@ -35,7 +36,7 @@ import torch
 from . import _ext
 from .models.vgg import VGGSpec
 from .ops import cpu_ref
-from .utils.arena import Arena
+from .utils.arena import Arena, block_map
 from .utils.streams import DevEvent, StreamJoin
 
 
@@ -159,7 +160,9 @@ class VGGEngine:
 
     def __init__(self, name: str = "VGG11", device="cuda", max_batch: int = 256, num_classes: int = 10,
                  lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 1e-4, bn_momentum: float = 0.1,
-                 bn_eps: float = 1e-5, in_hw: int = 32, backend=None, impl: str = "fp32"):
+                 bn_eps: float = 1e-5, in_hw: int = 32, backend=None, impl: str = "fp32",
+                 optimizer: Optional[str] = None, trust_coef: Optional[float] = None, lars_eps: float = 1e-9,
+                 clip_grad_norm: Optional[float] = None):
         self.device = torch.device(device)
         self.K = backend if backend is not None else (_ext.require() if self.device.type == "cuda" else cpu_ref)
         if impl not in IMPLS:
@@ -180,6 +183,19 @@ class VGGEngine:
         self.bn_momentum, self.bn_eps = bn_momentum, bn_eps
         self.num_classes = num_classes
         self.steps_taken = 0
+        # optimizer: "sgd" (the reference's, default) | "lars" (layer-wise trust ratios on every
+        # tensor of rank >= 2); clip_grad_norm > 0 clips the global gradient norm.  None: from the
+        # environment (DPA_OPTIMIZER, DPA_TRUST_COEF, DPA_CLIP_GRAD_NORM).
+        self.optimizer = optimizer if optimizer is not None else os.environ.get("DPA_OPTIMIZER", "sgd")
+        if self.optimizer not in ("sgd", "lars"):
+            raise ValueError("optimizer must be 'sgd' or 'lars'")
+        self.trust_coef = float(trust_coef if trust_coef is not None else os.environ.get("DPA_TRUST_COEF", "0.001"))
+        self.lars_eps = float(lars_eps)
+        self.clip_grad_norm = float(clip_grad_norm if clip_grad_norm is not None
+                                    else os.environ.get("DPA_CLIP_GRAD_NORM", "0"))
+        # LARS and clipping need the norms of the whole, fully reduced gradient arena: the update
+        # is then three launches over the arena (kernels/lars.hip), never a slice of it
+        self.whole_arena_step = self.optimizer == "lars" or self.clip_grad_norm > 0
         dev = self.device
         L = self.spec.convs
         entries = []
@@ -190,6 +206,13 @@ class VGGEngine:
         self.params = Arena(entries, dev)
         self.grads = self.params.like()
         self.mom = self.params.like()
+        if self.whole_arena_step:
+            self._opt_bmap, self._opt_segs = block_map(self.params.segments(), int(self.K.OPT_CHUNK),
+                                                       self.optimizer == "lars", dev)
+            nseg = self._opt_segs.shape[0]
+            self._opt_partials = torch.zeros(self._opt_bmap.shape[0], 2, dtype=torch.float64, device=dev)
+            self._opt_table = torch.ones(nseg + 1, dtype=torch.float32, device=dev)
+            self._opt_stats = torch.zeros(2 * nseg + 2, dtype=torch.float64, device=dev)
         self.buffers = Arena([(f"{l.bn_key}.{b}", (l.cout,)) for l in L for b in ("running_mean", "running_var")],
                              dev)
         self.nbt = torch.zeros(len(L), dtype=torch.int64, device=dev)
@@ -945,8 +968,33 @@ class VGGEngine:
         self._sgd(grad_scale, offset, count, self.steps_taken == 0 if first is None else first)
 
     def _sgd(self, grad_scale: float, offset: int, count: int, first: bool):
+        if self.whole_arena_step:
+            n = self.params.flat.numel()
+            if offset != 0 or (count >= 0 and count != n):
+                raise ValueError("sgd_step: LARS / gradient clipping update the whole arena (the norms of a "
+                                 f"slice are not defined); got offset={offset}, count={count}")
+            K, p, g = self.K, self.params.flat, self.grads.flat
+            K.sqnorm_partials(p, g, self._opt_bmap, self._opt_partials, self._opt_segs.shape[0])
+            K.lars_finalize(self._opt_partials, self._opt_segs, self._opt_table, self._opt_stats, grad_scale,
+                            self.clip_grad_norm, self.trust_coef, self.weight_decay, self.lars_eps)
+            K.sgd_segmented(p, g, self.mom.flat, self._opt_bmap, self._opt_table, self.lr, self.momentum,
+                            self.weight_decay, first, self.wplanes)
+            return
         self.K.sgd_flat(self.params.flat, self.grads.flat, self.mom.flat, self.lr, self.momentum, self.weight_decay,
                         grad_scale, first, offset, count, self.wplanes)
+
+    def opt_stats(self) -> dict:
+        """The last LARS / clipping step's norms as Python values (synchronises): ``grad_norm`` (of
+        the scaled gradient, before clipping), ``clip_coef``, and per tensor name ``p_norm``,
+        ``g_norm`` and ``trust_ratio`` under ``tensors``."""
+        if not self.whole_arena_step:
+            raise ValueError("opt_stats: the engine runs plain SGD (no LARS, no gradient clipping)")
+        st, tb = self._opt_stats.cpu().tolist(), self._opt_table.cpu().tolist()
+        names = self.params.names()
+        S = len(names)
+        return {"grad_norm": st[2 * S], "clip_coef": st[2 * S + 1],
+                "tensors": {n: {"p_norm": st[i], "g_norm": st[S + i], "trust_ratio": tb[i]}
+                            for i, n in enumerate(names)}}
 
     def wait_signal(self, signal):
         """The current stream waits (one polling wave, bounded) for a ``(flag, value)`` signal."""
@@ -991,7 +1039,7 @@ class VGGEngine:
     def _health_setup(self):
         names, addrs = [], []
         if self.np == 2:
-            for nm, a in zip(("conv", "bn", "sgd", "bn_fused"), self.K.h2_overflow_addrs()):
+            for nm, a in zip(("conv", "bn", "sgd", "bn_fused", "lars"), self.K.h2_overflow_addrs()):
                 names.append(f"fp16-pair overflow ({nm} kernels)")
                 addrs.append(a)
         if self.ksig_tmo is not None:

@@ -40,6 +40,67 @@ def sgd_flat(p, g, buf, lr, momentum, wd, gscale, first, offset=0, count=-1, pla
         planes[:, sl].copy_(split_bf16(pp, planes.shape[0]))
 
 
+OPT_CHUNK = 8192  # chunk length of the optimizer's block map (kernels/lars.hip)
+
+
+def sqnorm_partials(p, g, bmap, partials, nseg):
+    """partials[b] = (sum p^2, sum g^2) of chunk b in fp64 (bmap: utils/arena.block_map)."""
+    out = partials.view(-1, 2)
+    for b, (seg, start, ln) in enumerate(bmap.tolist()):
+        out[b, 0] = p[start:start + ln].double().square().sum()
+        out[b, 1] = g[start:start + ln].double().square().sum()
+
+
+def lars_finalize(partials, segs, table, stats, gscale, max_norm, trust_coef, wd, eps):
+    """Per-segment norms from the chunk partials, the clip coefficient (clip_grad_norm_ of the
+    scaled gradient) and the LARS trust ratios, all in fp64 (kernels/lars.hip (b)).
+    table: r_s per segment, then gmul = gscale * c.  stats: |p|_s, gscale |g|_s, gscale |g|, c."""
+    part = partials.view(-1, 2).double()
+    rows = segs.tolist()
+    S = len(rows)
+    P = [float(part[f:f + c, 0].sum()) for f, c, _ in rows]
+    Gs = [float(part[f:f + c, 1].sum()) for f, c, _ in rows]
+    G = 0.0
+    for v in Gs:
+        G += v
+    gnorm = gscale * math.sqrt(G)
+    c = min(1.0, max_norm / (gnorm + 1e-6)) if max_norm > 0 else 1.0
+    gmul = gscale * c
+    for s, (_, _, adapt) in enumerate(rows):
+        pn, gn = math.sqrt(P[s]), gmul * math.sqrt(Gs[s])
+        r = trust_coef * pn / (gn + wd * pn + eps) if adapt and pn > 0 and gn > 0 else 1.0
+        table[s] = r
+        stats[s] = pn
+        stats[S + s] = gscale * math.sqrt(Gs[s])
+    table[S] = gmul
+    stats[2 * S] = gnorm
+    stats[2 * S + 1] = c
+
+
+def sgd_segmented(p, g, buf, bmap, table, lr, momentum, wd, first, planes=None):
+    """sgd_flat over the chunks of bmap with the segment's trust ratio and the table's gradient
+    multiplier:  d = (g * gmul + wd * p) * r_s ; buf = first ? d : momentum * buf + d ; p -= lr * buf
+    (LARS with the learning rate outside the momentum, as apex LARC / torchlars)."""
+    S = table.numel() - 1
+    gmul = table[S].to(p.dtype)
+    r = torch.ones_like(p)
+    cov = torch.zeros(p.numel(), dtype=torch.bool)
+    for seg, start, ln in bmap.tolist():
+        r[start:start + ln] = table[seg].to(p.dtype)
+        cov[start:start + ln] = True
+    d = (g * gmul + wd * p) * r
+    nb = d if first else buf * momentum + d
+    if bool(cov.all()):
+        buf.copy_(nb)
+        p.sub_(lr * buf)
+    else:
+        buf[cov] = nb[cov]
+        p[cov] = p[cov] - lr * buf[cov]
+    if planes is not None:
+        pl = split_bf16(p, planes.shape[0])
+        planes[:, cov] = pl[:, cov]
+
+
 def split_bf16(x, np_):
     """fp32 -> [np_, *x.shape] bf16 planes (round-to-nearest-even), the HIP split's semantics."""
     out, r = [], x.float()

@@ -254,13 +254,45 @@ class DistributedDataParallel(nn.Module):
 
 class FlatSGD:
     """torch.optim.SGD semantics (momentum, dampening 0, weight decay, no nesterov) as ONE fused
-    kernel over the DDP arenas; ``step(grad_scale)`` folds the 1/W DDP scale in."""
+    kernel over the DDP arenas; ``step(grad_scale)`` folds the 1/W DDP scale in.
 
-    def __init__(self, ddp: DistributedDataParallel, lr: float, momentum: float = 0.0, weight_decay: float = 0.0):
+    ``trust_coef`` (not None): LARS, a trust ratio on every parameter of rank >= 2;
+    ``clip_grad_norm`` > 0: global-norm gradient clipping.  Either makes the step the three
+    launches of kernels/lars.hip over the wrapper's parameters as segments (fp32 arena on the GPU;
+    anything else runs ops/cpu_ref)."""
+
+    def __init__(self, ddp: DistributedDataParallel, lr: float, momentum: float = 0.0, weight_decay: float = 0.0,
+                 trust_coef: Optional[float] = None, clip_grad_norm: Optional[float] = None, lars_eps: float = 1e-9):
         self.ddp = ddp
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.buf = torch.zeros_like(ddp.flat_params)
         self.steps = 0
+        self.trust_coef, self.lars_eps = trust_coef, lars_eps
+        self.clip_grad_norm = float(clip_grad_norm or 0.0)
+        self.segmented = trust_coef is not None or self.clip_grad_norm > 0
+        if self.segmented:
+            from ..utils.arena import block_map
+
+            p = ddp.flat_params
+            self._native = p.is_cuda and p.dtype == torch.float32
+            K = self._backend()
+            segs = [(o, (q.numel() + ALIGN - 1) // ALIGN * ALIGN, q.ndim)
+                    for o, q in zip(ddp._pflat.offsets, ddp._params)]
+            self._bmap, self._segs = block_map(segs, int(K.OPT_CHUNK), trust_coef is not None, p.device)
+            nseg = self._segs.shape[0]
+            self._partials = torch.zeros(self._bmap.shape[0], 2, dtype=torch.float64, device=p.device)
+            # (the oracle path keeps the ratios in the arena's own precision)
+            self._table = torch.ones(nseg + 1, dtype=torch.float32 if self._native else p.dtype, device=p.device)
+            self._stats = torch.zeros(2 * nseg + 2, dtype=torch.float64, device=p.device)
+
+    def _backend(self):
+        if self._native:
+            from .. import _ext
+
+            return _ext.require()
+        from ..ops import cpu_ref
+
+        return cpu_ref
 
     def zero_grad(self, set_to_none: bool = False):
         self.ddp.zero_grad()
@@ -268,7 +300,14 @@ class FlatSGD:
     @torch.no_grad()
     def step(self, grad_scale: float = 1.0):
         p, g = self.ddp.flat_params, self.ddp.flat_grads
-        if p.is_cuda:
+        if self.segmented:
+            K = self._backend()
+            K.sqnorm_partials(p, g, self._bmap, self._partials, self._segs.shape[0])
+            K.lars_finalize(self._partials, self._segs, self._table, self._stats, grad_scale, self.clip_grad_norm,
+                            self.trust_coef or 0.0, self.weight_decay, self.lars_eps)
+            K.sgd_segmented(p, g, self.buf, self._bmap, self._table, self.lr, self.momentum, self.weight_decay,
+                            self.steps == 0, self.ddp.weight_planes if self._native else None)
+        elif p.is_cuda:
             from .. import _ext
 
             _ext.require().sgd_flat(p, g, self.buf, self.lr, self.momentum, self.weight_decay, grad_scale,

@@ -127,6 +127,13 @@ class GradSync:
         # take off the tail: DDP 166.5k vs 168.0k img/s, per-tensor all-reduce mode (34 buckets)
         # 114-125k vs 154k (docs/PERF_NOTES.md).
         fused = os.environ.get("DPA_FUSED_STEP", "0")
+        # LARS / gradient clipping (engine.whole_arena_step): the norms are defined only once every
+        # bucket is reduced, so the update is one whole-arena step after finish(), never per bucket
+        if getattr(engine, "whole_arena_step", False):
+            if self.fusable_step and overlap and fused != "0" and comm.rank == 0:
+                print(f"[sync] DPA_FUSED_STEP={fused} ignored: LARS / gradient clipping update the whole arena "
+                      "after the gradient sync", flush=True)
+            self.fusable_step = False
         self.fuse_step = overlap and self.fusable_step and (fused == "1" or (fused == "auto" and self.active))
         self._cuda = engine.device.type == "cuda"
         order = [["fc1.weight", "fc1.bias"]] + [
@@ -451,6 +458,10 @@ class ZeroSync(DDPSync):
 
     def __init__(self, engine, comm, bucket_mb: float = 10.0, overlap: bool = True, broadcast_init: bool = True,
                  broadcast_buffers: bool = True, tail_mb: float = 2.0):
+        if getattr(engine, "whole_arena_step", False) and comm.name != "null" and comm.world > 1:
+            raise ValueError("zero1 does not support LARS / gradient clipping: after the reduce-scatter each rank "
+                             "holds only its shards of the reduced gradient, so it cannot form the per-tensor and "
+                             "global norms (sharded norms are not implemented); use ddp, allreduce or gather")
         super().__init__(engine, comm, bucket_mb, overlap, broadcast_init, broadcast_buffers, tail_mb)
         if self.active:
             for b in self.buckets:
@@ -499,9 +510,12 @@ class ZeroSync(DDPSync):
         if not self.active:
             e.sgd_step(grad_scale)
             return
-        for b in self.buckets:  # the owned shards (compute stream, after finish()'s wait)
-            lo, sb = self._shard(b)
-            e.sgd_step(grad_scale, lo, sb)
+        if getattr(e, "whole_arena_step", False):  # (one rank: its shards are the whole arena)
+            e.sgd_step(grad_scale)
+        else:
+            for b in self.buckets:  # the owned shards (compute stream, after finish()'s wait)
+                lo, sb = self._shard(b)
+                e.sgd_step(grad_scale, lo, sb)
         with self.comm.region():
             for b in self.buckets:
                 lo, sb = self._shard(b)

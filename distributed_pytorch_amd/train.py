@@ -179,6 +179,14 @@ def add_common_args(ap: argparse.ArgumentParser):
     g.add_argument("--lr", type=float, default=0.1)
     g.add_argument("--momentum", type=float, default=0.9)
     g.add_argument("--weight-decay", type=float, default=1e-4)
+    g.add_argument("--optimizer", default=None, choices=["sgd", "lars"],
+                   help="sgd (the reference's, default) | lars: layer-wise trust ratios on conv / linear weights "
+                        "(default: DPA_OPTIMIZER or sgd)")
+    g.add_argument("--trust-coef", type=float, default=None, help="LARS trust coefficient (default: DPA_TRUST_COEF "
+                                                                  "or 0.001)")
+    g.add_argument("--lars-eps", type=float, default=1e-9)
+    g.add_argument("--clip-grad-norm", type=float, default=None,
+                   help="clip the global gradient norm to this value, 0 = off (default: DPA_CLIP_GRAD_NORM or 0)")
     g.add_argument("--seed", type=int, default=1)
     g.add_argument("--sampler-seed", type=int, default=0)
     g.add_argument("--data-root", default="./data")
@@ -254,7 +262,9 @@ def run(ctx: DistContext, mode: str, args):
                                 seed=args.seed * 7919 + ctx.rank)
     test_loader = DeviceLoader(test_set, args.batch_size, ctx.device, sampler=None, train=False)
     engine = VGGEngine(args.model, ctx.device, max_batch=args.batch_size, lr=args.lr, momentum=args.momentum,
-                       weight_decay=args.weight_decay, impl=args.impl)
+                       weight_decay=args.weight_decay, impl=args.impl, optimizer=getattr(args, "optimizer", None),
+                       trust_coef=getattr(args, "trust_coef", None), lars_eps=getattr(args, "lars_eps", 1e-9),
+                       clip_grad_norm=getattr(args, "clip_grad_norm", None))
     engine.init_parameters(seed=args.seed)
     start_epoch, start_batch = resume(ctx, engine, mode, args, len(train_loader))
     sync = make_sync(mode, engine, ctx.comm, bucket_mb=args.bucket_mb, overlap=not args.no_overlap)
@@ -290,6 +300,9 @@ def run(ctx: DistContext, mode: str, args):
                 rec["scaling_efficiency"] = stats["images_per_sec_rank"] / base
             if res:
                 rec["test_loss"], rec["test_correct"] = res
+            if engine.whole_arena_step and engine.steps_taken > 0:  # the epoch's last step
+                ost = engine.opt_stats()
+                rec["grad_norm"], rec["clip_coef"] = ost["grad_norm"], ost["clip_coef"]
             with open(args.json_metrics, "a") as f:
                 f.write(json.dumps(rec) + "\n")
         if budget is not None and budget <= 0:

@@ -50,8 +50,42 @@ class Arena:
         hi = max(self.offsets[n] + (self.numels[n] + ALIGN - 1) // ALIGN * ALIGN for n in names)
         return lo, hi
 
+    def segments(self) -> List[Tuple[int, int, int]]:
+        """The segment table in arena order: (offset, padded extent, tensor rank) per entry.  The
+        segments tile ``[0, numel)``; the padding is part of its entry's segment."""
+        return [(self.offsets[k], (self.numels[k] + ALIGN - 1) // ALIGN * ALIGN, len(self.shapes[k]))
+                for k in self.shapes]
+
     def __getitem__(self, name: str) -> torch.Tensor:
         return self.views[name]
 
     def __contains__(self, name: str) -> bool:
         return name in self.views
+
+
+def block_map(segments: Iterable[Tuple[int, int, int]], chunk: int, adapt: bool, device=None):
+    """The optimizer's block map of an arena (ops: sqnorm_partials / lars_finalize / sgd_segmented).
+
+    ``segments``: (offset, padded extent, tensor rank) per entry, ascending and disjoint.  Each
+    segment is cut into chunks of at most ``chunk`` elements (the last one may be shorter; every
+    length is a multiple of 64).  Returns two int64 tensors on ``device``:
+
+    * ``bmap [nblocks, 3]``: (segment, start, length) of every chunk;
+    * ``segs [nseg, 3]``: (first chunk, chunks, adapted) of every segment, where a segment is
+      adapted (gets a LARS trust ratio) when ``adapt`` is set and its tensor has rank >= 2.
+    """
+    if chunk <= 0 or chunk % ALIGN:
+        raise ValueError(f"block_map: chunk must be a positive multiple of {ALIGN}")
+    bmap, segs, end = [], [], 0
+    for s, (off, ext, rank) in enumerate(segments):
+        if off < end or off % ALIGN or ext <= 0 or ext % ALIGN:
+            raise ValueError(f"block_map: segment {s} (offset {off}, extent {ext}) is not an aligned, ascending range")
+        end = off + ext
+        first = len(bmap)
+        for start in range(off, end, chunk):
+            bmap.append((s, start, min(chunk, end - start)))
+        segs.append((first, len(bmap) - first, 1 if adapt and rank >= 2 else 0))
+    if not segs:
+        raise ValueError("block_map: no segments")
+    return (torch.tensor(bmap, dtype=torch.int64, device=device).reshape(-1, 3),
+            torch.tensor(segs, dtype=torch.int64, device=device).reshape(-1, 3))
