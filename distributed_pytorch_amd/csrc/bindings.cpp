@@ -47,7 +47,7 @@ int dpa_bn_bwd(const void* gsrc, int nsplit, void* g, const void* z, const float
 long dpa_wgrad0_part_floats(int N);
 int dpa_gap(const void* x, float* feat, int N, int HW, int C, int xbf, hipStream_t st);
 int dpa_ce(const float* logits, const long long* target, float* loss_row, float* dlogits, int* correct_row,
-           float* loss, float* acc, int N, int J, hipStream_t st);
+           float* loss, float* acc, int N, int J, hipStream_t st, float label_smoothing);
 int dpa_head_bwd_prep(const float* dlogits, const float* gout, float* dl, float* db, int N, int J, hipStream_t st);
 int dpa_gap_bwd(const float* dfeat, void* dx, int N, int HW, int C, int xbf, hipStream_t st);
 long dpa_conv0_part_floats(int N);
@@ -63,7 +63,7 @@ int dpa_bn_bwd_wgrad0(const float* gsrc, int nsplit, float* g, const float* z, c
 int dpa_fc_ce_train(const float* x, const float* w, const float* b, const long long* target, float* loss_row,
                     float* dlogits, float* dx, float* dw, float* db, float* loss_out, float* loss_accum, int B,
                     int Cin, int J, hipStream_t st, const float* bn_z, const float* bn_scale,
-                    const float* bn_shift, int parts);
+                    const float* bn_shift, int parts, float label_smoothing);
 int dpa_fc_ce_eval(const float* x, const float* w, const float* b, const long long* target, float* loss_row,
                    int* correct_row, float* logits, float* acc, int B, int Cin, int J, hipStream_t st);
 int dpa_x3_splits(int Kred, int splits);
@@ -813,8 +813,11 @@ void gap(Tensor x, Tensor feat) {
 }
 
 // logits [N,J] fp32, target [N] int64 -> loss_row [N], optional dlogits [N,J] = (softmax - onehot)/N,
-// optional correct_row [N] int32, loss [1] = batch mean, acc [2] += (loss, #correct)
-void softmax_ce(Tensor logits, Tensor target, Tensor loss_row, OptT dlogits, OptT correct_row, OptT loss, OptT acc) {
+// optional correct_row [N] int32, loss [1] = batch mean, acc [2] += (loss, #correct).
+// label_smoothing eps: torch's F.cross_entropy(label_smoothing=eps) loss rows and dlogits (head.hip)
+void softmax_ce(Tensor logits, Tensor target, Tensor loss_row, OptT dlogits, OptT correct_row, OptT loss, OptT acc,
+                double label_smoothing) {
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "softmax_ce: label_smoothing must be in [0, 1)");
   need(logits, "logits");
   need(loss_row, "loss_row");
   TORCH_CHECK(target.is_cuda() && target.scalar_type() == at::kLong && target.is_contiguous(), "target int64");
@@ -827,7 +830,7 @@ void softmax_ce(Tensor logits, Tensor target, Tensor loss_row, OptT dlogits, Opt
   }
   if (dlogits.has_value() && dlogits->defined()) TORCH_CHECK(dlogits->numel() == (int64_t)N * J, "dlogits [N,J]");
   chk(dpa_ce(fp(logits), reinterpret_cast<const long long*>(target.data_ptr<int64_t>()), fp(loss_row), ofp(dlogits),
-             cr, ofp(loss), ofp(acc), N, J, cur_stream()),
+             cr, ofp(loss), ofp(acc), N, J, cur_stream(), (float)label_smoothing),
       "softmax_ce");
 }
 
@@ -1003,9 +1006,12 @@ void bn_fused_bwd(Tensor gsrc, int64_t nsplit, Tensor z, bool pool, int64_t rmax
 
 // ---------------- classifier head ----------------
 // bn_z [B,2,2,Cin] fp32 + bn_scale/bn_shift [Cin] (optional): the features x [B,Cin] are computed
-// from the last conv's output (BN + ReLU + 2x2 max-pool) inside the head kernel and written to x
+// from the last conv's output (BN + ReLU + 2x2 max-pool) inside the head kernel and written to x.
+// label_smoothing eps: torch's F.cross_entropy(label_smoothing=eps) loss rows and dlogits (fc_ce.hip)
 void fc_ce_train(Tensor x, Tensor w, Tensor b, Tensor target, Tensor loss_row, Tensor dlogits, Tensor dx, Tensor dw,
-                 Tensor db, Tensor loss_out, OptT loss_accum, OptT bn_z, OptT bn_scale, OptT bn_shift, int64_t parts) {
+                 Tensor db, Tensor loss_out, OptT loss_accum, OptT bn_z, OptT bn_scale, OptT bn_shift, int64_t parts,
+                 double label_smoothing) {
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "fc_ce_train: label_smoothing must be in [0, 1)");
   TORCH_CHECK(parts >= 1 && parts <= 3, "fc_ce_train: parts must be 1 (rows), 2 (weight gradient) or 3 (both)");
   need(x, "x");
   need(target, "target", at::kLong);
@@ -1024,7 +1030,8 @@ void fc_ce_train(Tensor x, Tensor w, Tensor b, Tensor target, Tensor loss_row, T
   }
   chk(dpa_fc_ce_train(fp(x), fp(w), fp(b), reinterpret_cast<const long long*>(target.data_ptr<int64_t>()),
                       fp(loss_row), fp(dlogits), fp(dx), fp(dw), fp(db), fp(loss_out), ofp(loss_accum), B, Cin, J,
-                      cur_stream(), zp, zp ? fp(*bn_scale) : nullptr, zp ? fp(*bn_shift) : nullptr, (int)parts),
+                      cur_stream(), zp, zp ? fp(*bn_scale) : nullptr, zp ? fp(*bn_shift) : nullptr, (int)parts,
+                      (float)label_smoothing),
       "fc_ce_train");
 }
 
@@ -1354,7 +1361,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("trans_b") = false, py::arg("bias") = py::none(), py::arg("splits") = 1, py::arg("slab") = py::none());
   m.def("softmax_ce", &softmax_ce, py::arg("logits"), py::arg("target"), py::arg("loss_row"),
         py::arg("dlogits") = py::none(), py::arg("correct_row") = py::none(), py::arg("loss") = py::none(),
-        py::arg("acc") = py::none());
+        py::arg("acc") = py::none(), py::arg("label_smoothing") = 0.0);
   m.def("head_bwd_prep", &head_bwd_prep);
   m.def("gap_bwd", &gap_bwd);
   m.def("conv0_fwd", &conv0_fwd, py::arg("x"), py::arg("w"), py::arg("z"), py::arg("part") = py::none(),
@@ -1367,7 +1374,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("fc_ce_train", &fc_ce_train, py::arg("x"), py::arg("w"), py::arg("b"), py::arg("target"), py::arg("loss_row"),
         py::arg("dlogits"), py::arg("dx"), py::arg("dw"), py::arg("db"), py::arg("loss_out"), py::arg("loss_accum"),
         py::arg("bn_z") = py::none(), py::arg("bn_scale") = py::none(), py::arg("bn_shift") = py::none(),
-        py::arg("parts") = 3);
+        py::arg("parts") = 3, py::arg("label_smoothing") = 0.0);
   m.def("fc_ce_eval", &fc_ce_eval);
   m.def("augment", &augment);
   m.def("maxpool_fwd", &maxpool_fwd, py::arg("x"), py::arg("y"), py::arg("arg"), py::arg("k"), py::arg("s"),

@@ -4,6 +4,11 @@
 //
 // fc_ce_rows: one wavefront per sample row: logits (wave reductions over Cin), log-sum-exp,
 //   per-row loss, dlogits = (softmax - onehot)/B, and dx = dlogits @ W  — all in registers.
+//   With label smoothing eps (0 <= eps < 1; the SMOOTH training instances, torch's
+//   F.cross_entropy(label_smoothing=eps) with mean reduction and class-index targets):
+//     loss_row  = lse(z) - (1 - eps) * z_t - (eps / J) * sum_j z_j
+//     dlogits_j = (softmax_j - (1 - eps) * [j == t] - eps / J) / B
+//   Evaluation (fc_ce_eval) is always the plain cross-entropy.
 // fc_ce_wgrad: dW[j][c] = sum_b dlogits[b][j] * x[b][c], db[j] = sum_b dlogits[b][j], and the
 //   batch-mean loss (fixed summation order -> bitwise reproducible).
 #include "common.h"
@@ -28,14 +33,20 @@ struct BnIn {
   const float* shift;
 };
 
-template <bool TRAIN, int MAXJ, int MAXCL, bool BNIN = false>
+// Label smoothing: eps is a trailing kernel argument of the SMOOTH instances only (the pack is empty
+// otherwise), so the plain instances keep the argument list and the code they had before SMOOTH.
+__device__ __forceinline__ float eps_of(float e) { return e; }
+
+template <bool TRAIN, int MAXJ, int MAXCL, bool BNIN = false, bool SMOOTH = false, typename... Eps>
 __global__ __launch_bounds__(256) void fc_ce_rows_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ bias,
                                                          const long long* __restrict__ target,
                                                          float* __restrict__ loss_row, float* __restrict__ dlogits,
                                                          float* __restrict__ dx, int* __restrict__ correct_row,
                                                          float* __restrict__ logits_out, int B, int Cin, int J,
-                                                         BnIn bn = BnIn{nullptr, nullptr, nullptr}) {
+                                                         BnIn bn = BnIn{nullptr, nullptr, nullptr},
+                                                         Eps... eps_arg) {
+  static_assert(sizeof...(Eps) == (SMOOTH ? 1 : 0) && (!SMOOTH || TRAIN), "eps: SMOOTH training instances only");
   extern __shared__ float w_s[];  // [J][Cin]
   // All of the block's W loads are issued together, then the row's loads, and only then is the LDS
   // image written: one memory latency for both instead of one per 4 KB of W plus one for the row
@@ -119,8 +130,17 @@ __global__ __launch_bounds__(256) void fc_ce_rows_kernel(const float* __restrict
 #pragma unroll
   for (int j = 0; j < MAXJ; ++j)
     if (j == t) lt = logit[j];
+  float lr = lse - lt;
+  if constexpr (SMOOTH) {  // the wave holds all J logits: summed in ascending j (fixed order)
+    const float eps = eps_of(eps_arg...);
+    float sz = 0.f;
+#pragma unroll
+    for (int j = 0; j < MAXJ; ++j)
+      if (j < J) sz += logit[j];
+    lr = lse - (1.f - eps) * lt - eps / (float)J * sz;
+  }
   if (lane == 0) {
-    loss_row[row] = lse - lt;
+    loss_row[row] = lr;
     if (correct_row) correct_row[row] = (arg == t) ? 1 : 0;
   }
   if (logits_out && lane < J) {
@@ -132,7 +152,13 @@ __global__ __launch_bounds__(256) void fc_ce_rows_kernel(const float* __restrict
     const float invB = 1.f / (float)B;
     float dl[MAXJ];
 #pragma unroll
-    for (int j = 0; j < MAXJ; ++j) dl[j] = j < J ? (expf(logit[j] - lse) - (j == t ? 1.f : 0.f)) * invB : 0.f;
+    for (int j = 0; j < MAXJ; ++j) {
+      if constexpr (SMOOTH) {
+        const float eps = eps_of(eps_arg...);
+        dl[j] = j < J ? (expf(logit[j] - lse) - (j == t ? 1.f - eps : 0.f) - eps / (float)J) * invB : 0.f;
+      } else
+        dl[j] = j < J ? (expf(logit[j] - lse) - (j == t ? 1.f : 0.f)) * invB : 0.f;
+    }
     if (lane < J) {
 #pragma unroll
       for (int j = 0; j < MAXJ; ++j)
@@ -269,14 +295,28 @@ extern "C" {
 // parts: bit 0 = the row kernel (loss rows, dlogits, dx), bit 1 = the weight-gradient kernel (dW, db,
 // batch loss).  The VGG engine issues the row kernel on the critical path and the weight gradient on
 // its weight-gradient stream (nothing on the critical path reads dW, db or the loss).
+// label_smoothing (0 <= eps < 1, checked by the caller): eps != 0 runs the SMOOTH row kernels, eps == 0
+// the plain ones; only the row kernel sees it (the weight gradient reads dlogits and loss_row).
 int dpa_fc_ce_train(const float* x, const float* w, const float* b, const long long* target, float* loss_row,
                     float* dlogits, float* dx, float* dw, float* db, float* loss_out, float* loss_accum, int B,
                     int Cin, int J, hipStream_t st, const float* bn_z, const float* bn_scale, const float* bn_shift,
-                    int parts) {
+                    int parts, float label_smoothing) {
   if (J > GEN_J || Cin > 64 * GEN_CL || Cin % 4 || (long)B * J * 4 > 48 * 1024) return -2;
   const bool rows = parts & 1, wg = parts & 2;
-  if (bn_z) {
-    if (!bn_scale || !bn_shift || J > 10 || Cin > 512) return -2;
+  const float eps = label_smoothing;
+  if (bn_z && (!bn_scale || !bn_shift || J > 10 || Cin > 512)) return -2;
+  if (rows && eps != 0.f) {
+    const BnIn bn{bn_z, bn_scale, bn_shift};
+    if (bn_z)
+      fc_ce_rows_kernel<true, 10, 8, true, true><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
+          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, bn, eps);
+    else if (J <= 10 && Cin <= 512)
+      fc_ce_rows_kernel<true, 10, 8, false, true><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
+          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, bn, eps);
+    else
+      fc_ce_rows_kernel<true, GEN_J, GEN_CL, false, true><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
+          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, bn, eps);
+  } else if (bn_z) {
     if (rows)
       fc_ce_rows_kernel<true, 10, 8, true><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
           x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, BnIn{bn_z, bn_scale, bn_shift});

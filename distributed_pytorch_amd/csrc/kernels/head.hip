@@ -5,6 +5,10 @@
 //
 //   gap        feat[n][c] = mean_hw x[n][hw][c]            (x bf16 or fp32 NHWC, feat fp32)
 //   ce_rows    per row: log-sum-exp, loss_row, dlogits = (softmax - onehot(target)) / N
+//              with label smoothing eps (0 <= eps < 1, torch's F.cross_entropy(label_smoothing=eps)):
+//                loss_row  = lse(z) - (1 - eps) * z_t - (eps / J) * sum_j z_j
+//                dlogits_j = (softmax_j - (1 - eps) * [j == t] - eps / J) / N
+//              (training only: evaluation calls it with eps = 0, the plain cross-entropy)
 //   ce_finish  loss = sum_n loss_row[n]  (fixed order)     ; optional running accumulator
 //   bwd_prep   dl = dlogits * dloss ; db[j] = sum_n dl[n][j]   (fixed order)
 //   gap_bwd    dx[n][hw][c] = dfeat[n][c] / HW               (x's dtype)
@@ -57,13 +61,22 @@ __global__ __launch_bounds__(256) void gap_kernel(const T* __restrict__ x, float
   reinterpret_cast<float4*>(feat)[i] = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
 }
 
-// one 256-thread block per row; J up to any size (strided), block reductions in LDS (fixed order)
+// Label smoothing: eps is a trailing kernel argument of the SMOOTH instance only (the pack is empty
+// otherwise), so the plain instance keeps the argument list and the code it had before SMOOTH.
+__device__ __forceinline__ float eps_of(float e) { return e; }
+
+// one 256-thread block per row; J up to any size (strided), block reductions in LDS (fixed order).
+// SMOOTH: sum_j z_j rides in the sum-of-exp pass and its block reduction (a second LDS array).
+template <bool SMOOTH, typename... Eps>
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits,
                                                       const long long* __restrict__ target,
                                                       float* __restrict__ loss_row, float* __restrict__ dlogits,
-                                                      int* __restrict__ correct_row, int N, int J) {
+                                                      int* __restrict__ correct_row, int N, int J,
+                                                      Eps... eps_arg) {
+  static_assert(sizeof...(Eps) == (SMOOTH ? 1 : 0), "eps: the SMOOTH instance only");
   __shared__ float red[256];
   __shared__ int redi[256];
+  __shared__ float redz[SMOOTH ? 256 : 1];
   const int n = blockIdx.x, t = threadIdx.x;
   const float* lr = logits + (long)n * J;
   float mx = -INFINITY;
@@ -93,25 +106,46 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
   const int amax = redi[0];
   __syncthreads();
   float se = 0.f;
-  for (int j = t; j < J; j += 256) se += __expf(lr[j] - m);
+  if constexpr (SMOOTH) {
+    float sz = 0.f;
+    for (int j = t; j < J; j += 256) {
+      const float v = lr[j];
+      se += __expf(v - m);
+      sz += v;
+    }
+    redz[t] = sz;
+  } else {
+    for (int j = t; j < J; j += 256) se += __expf(lr[j] - m);
+  }
   red[t] = se;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
+    if (t < o) {
+      red[t] += red[t + o];
+      if constexpr (SMOOTH) redz[t] += redz[t + o];
+    }
     __syncthreads();
   }
   const float sum = red[0];
   const long long tg = target[n];
   const float lse = m + __logf(sum);
   if (t == 0) {
-    loss_row[n] = lse - lr[tg];
+    if constexpr (SMOOTH) {
+      const float eps = eps_of(eps_arg...);
+      loss_row[n] = lse - (1.f - eps) * lr[tg] - eps / (float)J * redz[0];
+    } else
+      loss_row[n] = lse - lr[tg];
     if (correct_row) correct_row[n] = amax == (int)tg ? 1 : 0;
   }
   if (dlogits) {
     const float invN = 1.f / (float)N, inv = 1.f / sum;
     for (int j = t; j < J; j += 256) {
       const float p = __expf(lr[j] - m) * inv;
-      dlogits[(long)n * J + j] = (p - (j == tg ? 1.f : 0.f)) * invN;
+      if constexpr (SMOOTH) {
+        const float eps = eps_of(eps_arg...);
+        dlogits[(long)n * J + j] = (p - (j == tg ? 1.f - eps : 0.f) - eps / (float)J) * invN;
+      } else
+        dlogits[(long)n * J + j] = (p - (j == tg ? 1.f : 0.f)) * invN;
     }
   }
 }
@@ -211,8 +245,12 @@ int dpa_gap(const void* x, float* feat, int N, int HW, int C, int xbf, hipStream
 }
 
 int dpa_ce(const float* logits, const long long* target, float* loss_row, float* dlogits, int* correct_row,
-           float* loss, float* acc, int N, int J, hipStream_t st) {
-  ce_rows_kernel<<<N, 256, 0, st>>>(logits, target, loss_row, dlogits, correct_row, N, J);
+           float* loss, float* acc, int N, int J, hipStream_t st, float label_smoothing) {
+  // label_smoothing (0 <= eps < 1, checked by the caller): eps != 0 runs the SMOOTH row kernel
+  if (label_smoothing != 0.f)
+    ce_rows_kernel<true><<<N, 256, 0, st>>>(logits, target, loss_row, dlogits, correct_row, N, J, label_smoothing);
+  else
+    ce_rows_kernel<false><<<N, 256, 0, st>>>(logits, target, loss_row, dlogits, correct_row, N, J);
   ce_finish_kernel<<<1, 256, 0, st>>>(loss_row, correct_row, N, loss, acc);
   return (int)hipGetLastError();
 }

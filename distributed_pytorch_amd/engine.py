@@ -162,7 +162,7 @@ class VGGEngine:
                  lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 1e-4, bn_momentum: float = 0.1,
                  bn_eps: float = 1e-5, in_hw: int = 32, backend=None, impl: str = "fp32",
                  optimizer: Optional[str] = None, trust_coef: Optional[float] = None, lars_eps: float = 1e-9,
-                 clip_grad_norm: Optional[float] = None):
+                 clip_grad_norm: Optional[float] = None, label_smoothing: Optional[float] = None):
         self.device = torch.device(device)
         self.K = backend if backend is not None else (_ext.require() if self.device.type == "cuda" else cpu_ref)
         if impl not in IMPLS:
@@ -196,6 +196,13 @@ class VGGEngine:
         # LARS and clipping need the norms of the whole, fully reduced gradient arena: the update
         # is then three launches over the arena (kernels/lars.hip), never a slice of it
         self.whole_arena_step = self.optimizer == "lars" or self.clip_grad_norm > 0
+        # label smoothing of the TRAINING loss (F.cross_entropy(label_smoothing=eps): the head kernel
+        # forms the smoothed loss rows and their gradient); None: from the environment
+        # (DPA_LABEL_SMOOTHING, default 0).  Evaluation is always the plain cross-entropy.
+        self.label_smoothing = float(label_smoothing if label_smoothing is not None
+                                     else os.environ.get("DPA_LABEL_SMOOTHING", "0"))
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {self.label_smoothing}")
         dev = self.device
         L = self.spec.convs
         entries = []
@@ -803,7 +810,9 @@ class VGGEngine:
         head_side = bool(epoch) and self.wstream is not None and self.head_side
         head_args = (feat, P["fc1.weight"], P["fc1.bias"], target, self.loss_row[:n], self.dlogits[:n],
                      self.g[-1][:n].view(n, -1), G["fc1.weight"], G["fc1.bias"], self.loss, self.loss_accum)
-        K.fc_ce_train(*head_args, **bn_in, **({"parts": 1} if head_side else {}))
+        # label smoothing: an argument of the row kernel only (parts=2 below reads dlogits / loss_row)
+        smooth = {"label_smoothing": self.label_smoothing} if self.label_smoothing else {}
+        K.fc_ce_train(*head_args, **bn_in, **({"parts": 1} if head_side else {}), **smooth)
         if grad_ready is not None and not head_side:
             grad_ready(["fc1.weight", "fc1.bias"])
         # Kernel-start signals (epoch > 0, signal.hip): each BN backward raises bsig[i] when it starts,

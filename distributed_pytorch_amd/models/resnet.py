@@ -61,11 +61,15 @@ class Bottleneck(nn.Module):
 
 class ResNet(nn.Module):
     """Input NHWC fp32 [N,H,W,3]; output logits [N, num_classes] (fp32).  With impl "bf16" the
-    activations between layers are bf16 tensors; parameters, BN statistics and the head are fp32."""
+    activations between layers are bf16 tensors; parameters, BN statistics and the head are fp32.
+    ``label_smoothing`` (0 <= eps < 1) smooths the loss of ``forward(x, target)`` as
+    ``F.cross_entropy(label_smoothing=eps)`` does; the logits of ``forward(x)`` do not depend on it."""
 
-    def __init__(self, layers: List[int], num_classes: int = 1000, impl: str = "bf16"):
+    def __init__(self, layers: List[int], num_classes: int = 1000, impl: str = "bf16",
+                 label_smoothing: float = 0.0):
         super().__init__()
         self.impl = impl
+        self.label_smoothing = Fn.check_label_smoothing(label_smoothing)
         self.conv1 = Conv2d(3, 64, 7, 2, 3, impl)
         self.bn1 = BatchNorm2d(64, "relu")
         self.maxpool = MaxPool2d(3, 2, 1)
@@ -97,17 +101,17 @@ class ResNet(nn.Module):
         return self.layer4(self.layer3(self.layer2(self.layer1(x))))
 
     def forward(self, x, target=None):
-        """Logits, or with ``target`` the batch-mean cross-entropy through the fused head."""
+        """Logits, or with ``target`` the batch-mean (label-smoothed) cross-entropy through the fused head."""
         if self.training:
             Fn.clear_deferred()
         f = self.features(x)
         if target is not None:
-            return Fn.head_ce(f, self.fc.weight, self.fc.bias, target)
+            return Fn.head_ce(f, self.fc.weight, self.fc.bias, target, self.label_smoothing)
         return Fn.head_logits(f, self.fc.weight, self.fc.bias)
 
 
-def resnet50(num_classes: int = 1000, impl: str = "bf16") -> ResNet:
-    return ResNet(LAYERS["resnet50"], num_classes, impl)
+def resnet50(num_classes: int = 1000, impl: str = "bf16", label_smoothing: float = 0.0) -> ResNet:
+    return ResNet(LAYERS["resnet50"], num_classes, impl, label_smoothing)
 
 
 # ---------------------------------------------------------------- stock-torch oracle (NCHW)

@@ -242,16 +242,27 @@ def bn_bwd_wgrad0(gsrc, nsplit, g, z, scale, shift, mean, invstd, gamma, part, c
 
 # ---------------------------------------------------------------- classifier head
 def fc_ce_train(x, w, b, target, loss_row, dlogits, dx, dw, db, loss_out, loss_accum, bn_z=None, bn_scale=None,
-                bn_shift=None):
+                bn_shift=None, label_smoothing=0.0):
+    """Linear + softmax cross-entropy (mean), forward and backward (native: fc_ce.hip).  With
+    label_smoothing eps (torch's F.cross_entropy(label_smoothing=eps)):
+    loss_row = lse(z) - (1 - eps) z_t - (eps / J) sum_j z_j,
+    dlogits_j = (softmax_j - (1 - eps) [j == t] - eps / J) / B."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError("label_smoothing must be in [0, 1)")
     B = x.shape[0]
     if bn_z is not None:  # features from the last conv's z: BN + ReLU + 2x2 max-pool, written to x
         x.copy_(torch.relu(bn_z * bn_scale + bn_shift).reshape(B, 4, -1).amax(1))
     logits = x @ w.t() + b
     lse = torch.logsumexp(logits, 1)
     lr = lse - logits.gather(1, target.view(-1, 1)).squeeze(1)
+    if eps:
+        lr = lse - (1.0 - eps) * logits.gather(1, target.view(-1, 1)).squeeze(1) - eps * logits.mean(1)
     loss_row.copy_(lr)
     p = torch.softmax(logits, 1)
-    p[torch.arange(B), target] -= 1.0
+    p[torch.arange(B), target] -= 1.0 - eps
+    if eps:
+        p -= eps / logits.shape[1]
     p /= B
     dlogits.copy_(p.reshape(dlogits.shape))
     dx.copy_(p @ w)

@@ -801,22 +801,26 @@ class HeadCE(torch.autograd.Function):
     into the optimizer arena when the DDP wrapper offers a slot (``grad_slot``)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, target):
+    def forward(ctx, x, weight, bias, target, label_smoothing=0.0):
         N = x.shape[0]
+        eps = float(label_smoothing)
         note_use(weight)
         note_use(bias)
         feat, logits = _head_fwd(x, weight, bias)
         if not _native(x):
-            loss = F.cross_entropy(logits, target)
+            loss = F.cross_entropy(logits, target, label_smoothing=eps)
             p = torch.softmax(logits, 1)
-            p[torch.arange(N), target] -= 1.0
+            p[torch.arange(N), target] -= 1.0 - eps
+            if eps:
+                p -= eps / logits.shape[1]
             dlogits = p / N
         else:
             dev = x.device
             loss_row = torch.empty(N, device=dev, dtype=torch.float32)
             dlogits = torch.empty_like(logits)
             loss = torch.empty((), device=dev, dtype=torch.float32)
-            _ext.require().softmax_ce(logits, target, loss_row, dlogits, None, loss.view(1), None)
+            _ext.require().softmax_ce(logits, target, loss_row, dlogits, None, loss.view(1), None,
+                                      label_smoothing=eps)
         ctx.save_for_backward(feat, dlogits, weight)
         ctx.w_b, ctx.x_meta = (weight, bias), (x.shape, x.dtype)
         return loss
@@ -826,12 +830,23 @@ class HeadCE(torch.autograd.Function):
         feat, dlogits, weight = ctx.saved_tensors
         g = gloss.reshape(1).to(dtype=feat.dtype).contiguous()
         dx, dw, db = _head_bwd(dlogits, g, feat, weight, *ctx.w_b, *ctx.x_meta)
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
-def head_ce(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-    """Batch-mean cross-entropy of Linear(GAP(x)) (x NHWC bf16/fp32; weight [J,C], bias [J] fp32)."""
-    return HeadCE.apply(x.contiguous(), weight, bias, target.contiguous())
+def check_label_smoothing(label_smoothing) -> float:
+    """The label-smoothing factor as a float; ValueError unless 0 <= eps < 1."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
+    return eps
+
+
+def head_ce(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, target: torch.Tensor,
+            label_smoothing: float = 0.0) -> torch.Tensor:
+    """Batch-mean cross-entropy of Linear(GAP(x)) (x NHWC bf16/fp32; weight [J,C], bias [J] fp32);
+    ``label_smoothing`` as in ``F.cross_entropy`` (mean reduction, class-index targets)."""
+    eps = check_label_smoothing(label_smoothing)
+    return HeadCE.apply(x.contiguous(), weight, bias, target.contiguous(), eps)
 
 
 def head_logits(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:

@@ -187,6 +187,10 @@ def add_common_args(ap: argparse.ArgumentParser):
     g.add_argument("--lars-eps", type=float, default=1e-9)
     g.add_argument("--clip-grad-norm", type=float, default=None,
                    help="clip the global gradient norm to this value, 0 = off (default: DPA_CLIP_GRAD_NORM or 0)")
+    g.add_argument("--label-smoothing", type=float, default=None,
+                   help="label smoothing of the training loss, 0 <= eps < 1, as in "
+                        "nn.CrossEntropyLoss(label_smoothing=eps); the test loss stays the plain cross-entropy "
+                        "(default: DPA_LABEL_SMOOTHING or 0)")
     g.add_argument("--seed", type=int, default=1)
     g.add_argument("--sampler-seed", type=int, default=0)
     g.add_argument("--data-root", default="./data")
@@ -251,6 +255,15 @@ def resume(ctx: DistContext, engine: VGGEngine, mode: str, args, n_batches: int)
     return start_epoch, start_batch
 
 
+def build_engine(args, device) -> VGGEngine:
+    """The engine the command line describes (options left out: the engine's environment defaults)."""
+    return VGGEngine(args.model, device, max_batch=args.batch_size, lr=args.lr, momentum=args.momentum,
+                     weight_decay=args.weight_decay, impl=args.impl, optimizer=getattr(args, "optimizer", None),
+                     trust_coef=getattr(args, "trust_coef", None), lars_eps=getattr(args, "lars_eps", 1e-9),
+                     clip_grad_norm=getattr(args, "clip_grad_norm", None),
+                     label_smoothing=getattr(args, "label_smoothing", None))
+
+
 def run(ctx: DistContext, mode: str, args):
     if args.trace:
         enable_tracing(True)
@@ -261,10 +274,7 @@ def run(ctx: DistContext, mode: str, args):
     train_loader = DeviceLoader(train_set, args.batch_size, ctx.device, sampler=sampler, train=True,
                                 seed=args.seed * 7919 + ctx.rank)
     test_loader = DeviceLoader(test_set, args.batch_size, ctx.device, sampler=None, train=False)
-    engine = VGGEngine(args.model, ctx.device, max_batch=args.batch_size, lr=args.lr, momentum=args.momentum,
-                       weight_decay=args.weight_decay, impl=args.impl, optimizer=getattr(args, "optimizer", None),
-                       trust_coef=getattr(args, "trust_coef", None), lars_eps=getattr(args, "lars_eps", 1e-9),
-                       clip_grad_norm=getattr(args, "clip_grad_norm", None))
+    engine = build_engine(args, ctx.device)
     engine.init_parameters(seed=args.seed)
     start_epoch, start_batch = resume(ctx, engine, mode, args, len(train_loader))
     sync = make_sync(mode, engine, ctx.comm, bucket_mb=args.bucket_mb, overlap=not args.no_overlap)
@@ -300,6 +310,8 @@ def run(ctx: DistContext, mode: str, args):
                 rec["scaling_efficiency"] = stats["images_per_sec_rank"] / base
             if res:
                 rec["test_loss"], rec["test_correct"] = res
+            if engine.label_smoothing:  # train_loss is then the smoothed loss, test_loss the plain one
+                rec["label_smoothing"] = engine.label_smoothing
             if engine.whole_arena_step and engine.steps_taken > 0:  # the epoch's last step
                 ost = engine.opt_stats()
                 rec["grad_norm"], rec["clip_coef"] = ost["grad_norm"], ost["clip_coef"]
