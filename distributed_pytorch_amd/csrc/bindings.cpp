@@ -47,7 +47,8 @@ int dpa_bn_bwd(const void* gsrc, int nsplit, void* g, const void* z, const float
 long dpa_wgrad0_part_floats(int N);
 int dpa_gap(const void* x, float* feat, int N, int HW, int C, int xbf, hipStream_t st);
 int dpa_ce(const float* logits, const long long* target, float* loss_row, float* dlogits, int* correct_row,
-           float* loss, float* acc, int N, int J, hipStream_t st, float label_smoothing);
+           float* loss, float* acc, int N, int J, hipStream_t st, float label_smoothing, const long long* target2,
+           const float* lam);
 int dpa_head_bwd_prep(const float* dlogits, const float* gout, float* dl, float* db, int N, int J, hipStream_t st);
 int dpa_gap_bwd(const float* dfeat, void* dx, int N, int HW, int C, int xbf, hipStream_t st);
 long dpa_conv0_part_floats(int N);
@@ -63,7 +64,8 @@ int dpa_bn_bwd_wgrad0(const float* gsrc, int nsplit, float* g, const float* z, c
 int dpa_fc_ce_train(const float* x, const float* w, const float* b, const long long* target, float* loss_row,
                     float* dlogits, float* dx, float* dw, float* db, float* loss_out, float* loss_accum, int B,
                     int Cin, int J, hipStream_t st, const float* bn_z, const float* bn_scale,
-                    const float* bn_shift, int parts, float label_smoothing);
+                    const float* bn_shift, int parts, float label_smoothing, const long long* target2,
+                    const float* lam);
 int dpa_fc_ce_eval(const float* x, const float* w, const float* b, const long long* target, float* loss_row,
                    int* correct_row, float* logits, float* acc, int B, int Cin, int J, hipStream_t st);
 int dpa_x3_splits(int Kred, int splits);
@@ -120,6 +122,10 @@ int dpa_maxpool_bwd(const void* dy, const unsigned char* arg, void* dx, int N, i
 int dpa_augment(const unsigned char* img, const long long* idx, const long long* labels, float* out,
                 long long* target, int B, int Hs, int Ws, int pad, int train, unsigned long long seed,
                 unsigned long long salt, const float* mean, const float* std, hipStream_t st);
+int dpa_augment_mix(const unsigned char* img, const long long* idx, const long long* labels, float* out,
+                    long long* target, long long* target2, float* lam_out, int mode, float lam, int y0, int y1,
+                    int x0, int x1, int B, int Hs, int Ws, int pad, unsigned long long seed, unsigned long long salt,
+                    const float* mean, const float* std, hipStream_t st);
 }
 
 namespace {
@@ -170,6 +176,24 @@ void need(const Tensor& t, const char* name, at::ScalarType dt = at::kFloat) {
 
 float* fp(const Tensor& t) { return t.data_ptr<float>(); }
 float* ofp(const OptT& t) { return t.has_value() && t->defined() ? t->data_ptr<float>() : nullptr; }
+
+// Mixup / CutMix pair targets of the loss heads: target2 int64 [B] and lam float32 [B], both or neither,
+// on the logits' device.  Returns target2's pointer (null: no mix) and sets *lam_p.
+const long long* mix_targets(const OptT& target2, const OptT& lam, int64_t B, const Tensor& like, const char* what,
+                             const float** lam_p) {
+  const bool h2 = target2.has_value() && target2->defined(), hl = lam.has_value() && lam->defined();
+  TORCH_CHECK(h2 == hl, what, ": target2 and lam must be given together");
+  *lam_p = nullptr;
+  if (!h2) return nullptr;
+  need(*target2, "target2", at::kLong);
+  need(*lam, "lam");
+  TORCH_CHECK(target2->dim() == 1 && target2->numel() == B, what, ": target2 must be int64 [B]");
+  TORCH_CHECK(lam->dim() == 1 && lam->numel() == B, what, ": lam must be float32 [B]");
+  TORCH_CHECK(target2->device() == like.device() && lam->device() == like.device(), what,
+              ": target2 and lam must be on the logits' device");
+  *lam_p = fp(*lam);
+  return reinterpret_cast<const long long*>(target2->data_ptr<int64_t>());
+}
 
 // ---------------- optimizer / elementwise ----------------
 // planes (optional): bf16 [NP, p.numel()] operand planes of the whole arena, refreshed in the same pass
@@ -815,8 +839,9 @@ void gap(Tensor x, Tensor feat) {
 // logits [N,J] fp32, target [N] int64 -> loss_row [N], optional dlogits [N,J] = (softmax - onehot)/N,
 // optional correct_row [N] int32, loss [1] = batch mean, acc [2] += (loss, #correct).
 // label_smoothing eps: torch's F.cross_entropy(label_smoothing=eps) loss rows and dlogits (head.hip)
+// target2 / lam (both or neither): probability targets lam * onehot(target) + (1 - lam) * onehot(target2)
 void softmax_ce(Tensor logits, Tensor target, Tensor loss_row, OptT dlogits, OptT correct_row, OptT loss, OptT acc,
-                double label_smoothing) {
+                double label_smoothing, OptT target2, OptT lam) {
   TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "softmax_ce: label_smoothing must be in [0, 1)");
   need(logits, "logits");
   need(loss_row, "loss_row");
@@ -829,8 +854,10 @@ void softmax_ce(Tensor logits, Tensor target, Tensor loss_row, OptT dlogits, Opt
     cr = correct_row->data_ptr<int>();
   }
   if (dlogits.has_value() && dlogits->defined()) TORCH_CHECK(dlogits->numel() == (int64_t)N * J, "dlogits [N,J]");
+  const float* lp = nullptr;
+  const long long* t2 = mix_targets(target2, lam, N, logits, "softmax_ce", &lp);
   chk(dpa_ce(fp(logits), reinterpret_cast<const long long*>(target.data_ptr<int64_t>()), fp(loss_row), ofp(dlogits),
-             cr, ofp(loss), ofp(acc), N, J, cur_stream(), (float)label_smoothing),
+             cr, ofp(loss), ofp(acc), N, J, cur_stream(), (float)label_smoothing, t2, lp),
       "softmax_ce");
 }
 
@@ -1008,9 +1035,11 @@ void bn_fused_bwd(Tensor gsrc, int64_t nsplit, Tensor z, bool pool, int64_t rmax
 // bn_z [B,2,2,Cin] fp32 + bn_scale/bn_shift [Cin] (optional): the features x [B,Cin] are computed
 // from the last conv's output (BN + ReLU + 2x2 max-pool) inside the head kernel and written to x.
 // label_smoothing eps: torch's F.cross_entropy(label_smoothing=eps) loss rows and dlogits (fc_ce.hip)
+// target2 / lam (both or neither; Mixup / CutMix): probability targets lam * onehot(target) + (1 - lam) *
+// onehot(target2), lam read per row on the device
 void fc_ce_train(Tensor x, Tensor w, Tensor b, Tensor target, Tensor loss_row, Tensor dlogits, Tensor dx, Tensor dw,
                  Tensor db, Tensor loss_out, OptT loss_accum, OptT bn_z, OptT bn_scale, OptT bn_shift, int64_t parts,
-                 double label_smoothing) {
+                 double label_smoothing, OptT target2, OptT lam) {
   TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "fc_ce_train: label_smoothing must be in [0, 1)");
   TORCH_CHECK(parts >= 1 && parts <= 3, "fc_ce_train: parts must be 1 (rows), 2 (weight gradient) or 3 (both)");
   need(x, "x");
@@ -1028,10 +1057,12 @@ void fc_ce_train(Tensor x, Tensor w, Tensor b, Tensor target, Tensor loss_row, T
     need(*bn_shift, "bn_shift");
     zp = fp(*bn_z);
   }
+  const float* lp = nullptr;
+  const long long* t2 = mix_targets(target2, lam, B, x, "fc_ce_train", &lp);
   chk(dpa_fc_ce_train(fp(x), fp(w), fp(b), reinterpret_cast<const long long*>(target.data_ptr<int64_t>()),
                       fp(loss_row), fp(dlogits), fp(dx), fp(dw), fp(db), fp(loss_out), ofp(loss_accum), B, Cin, J,
                       cur_stream(), zp, zp ? fp(*bn_scale) : nullptr, zp ? fp(*bn_shift) : nullptr, (int)parts,
-                      (float)label_smoothing),
+                      (float)label_smoothing, t2, lp),
       "fc_ce_train");
 }
 
@@ -1070,6 +1101,42 @@ void augment(Tensor images, Tensor idx, Tensor labels, Tensor out, OptT target, 
                   reinterpret_cast<const long long*>(labels.data_ptr<int64_t>()), fp(out), tp, B, Hs, Ws, (int)pad,
                   train ? 1 : 0, (unsigned long long)seed, (unsigned long long)salt, m, s, cur_stream()),
       "augment");
+}
+
+// Training augmentation with Mixup (mode 0) or CutMix (mode 1, box [y0,y1) x [x0,x1)) against slot
+// B-1-b: out as augment; target / target2 int64 [B], lam_out float32 [B] (augment.hip).
+void augment_mix(Tensor images, Tensor idx, Tensor labels, Tensor out, Tensor target, Tensor target2, Tensor lam_out,
+                 int64_t pad, int64_t seed, int64_t salt, std::vector<double> mean, std::vector<double> std_,
+                 int64_t mode, double lam, int64_t y0, int64_t y1, int64_t x0, int64_t x1) {
+  need(images, "images", at::kByte);
+  need(idx, "idx", at::kLong);
+  need(labels, "labels", at::kLong);
+  need(out, "out");
+  need(target, "target", at::kLong);
+  need(target2, "target2", at::kLong);
+  need(lam_out, "lam_out");
+  TORCH_CHECK(images.dim() == 4 && images.size(3) == 3, "augment_mix: images must be [N,H,W,3] uint8");
+  const int B = idx.numel(), Hs = images.size(1), Ws = images.size(2);
+  TORCH_CHECK(B >= 1, "augment_mix: empty batch");
+  TORCH_CHECK(out.numel() == (int64_t)B * Hs * Ws * 4, "augment_mix: out must be [B,H,W,4]");
+  TORCH_CHECK(target.numel() == B && target2.numel() == B && lam_out.numel() == B,
+              "augment_mix: target, target2 and lam_out must be [B]");
+  TORCH_CHECK(mode == 0 || mode == 1, "augment_mix: mode must be 0 (Mixup) or 1 (CutMix)");
+  TORCH_CHECK(lam >= 0.0 && lam <= 1.0, "augment_mix: lam must be in [0, 1]");
+  TORCH_CHECK(mode == 0 || (0 <= y0 && y0 <= y1 && y1 <= Hs && 0 <= x0 && x0 <= x1 && x1 <= Ws),
+              "augment_mix: the box must lie inside the image");
+  float m[3], s[3];
+  for (int c = 0; c < 3; ++c) {
+    m[c] = (float)mean.at(c);
+    s[c] = (float)std_.at(c);
+  }
+  chk(dpa_augment_mix(images.data_ptr<uint8_t>(), reinterpret_cast<const long long*>(idx.data_ptr<int64_t>()),
+                      reinterpret_cast<const long long*>(labels.data_ptr<int64_t>()), fp(out),
+                      reinterpret_cast<long long*>(target.data_ptr<int64_t>()),
+                      reinterpret_cast<long long*>(target2.data_ptr<int64_t>()), fp(lam_out), (int)mode, (float)lam,
+                      (int)y0, (int)y1, (int)x0, (int)x1, B, Hs, Ws, (int)pad, (unsigned long long)seed,
+                      (unsigned long long)salt, m, s, cur_stream()),
+      "augment_mix");
 }
 
 // ---------------- NHWC max-pool (generic path) ----------------
@@ -1361,7 +1428,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("trans_b") = false, py::arg("bias") = py::none(), py::arg("splits") = 1, py::arg("slab") = py::none());
   m.def("softmax_ce", &softmax_ce, py::arg("logits"), py::arg("target"), py::arg("loss_row"),
         py::arg("dlogits") = py::none(), py::arg("correct_row") = py::none(), py::arg("loss") = py::none(),
-        py::arg("acc") = py::none(), py::arg("label_smoothing") = 0.0);
+        py::arg("acc") = py::none(), py::arg("label_smoothing") = 0.0, py::arg("target2") = py::none(),
+        py::arg("lam") = py::none());
   m.def("head_bwd_prep", &head_bwd_prep);
   m.def("gap_bwd", &gap_bwd);
   m.def("conv0_fwd", &conv0_fwd, py::arg("x"), py::arg("w"), py::arg("z"), py::arg("part") = py::none(),
@@ -1374,9 +1442,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("fc_ce_train", &fc_ce_train, py::arg("x"), py::arg("w"), py::arg("b"), py::arg("target"), py::arg("loss_row"),
         py::arg("dlogits"), py::arg("dx"), py::arg("dw"), py::arg("db"), py::arg("loss_out"), py::arg("loss_accum"),
         py::arg("bn_z") = py::none(), py::arg("bn_scale") = py::none(), py::arg("bn_shift") = py::none(),
-        py::arg("parts") = 3, py::arg("label_smoothing") = 0.0);
+        py::arg("parts") = 3, py::arg("label_smoothing") = 0.0, py::arg("target2") = py::none(),
+        py::arg("lam") = py::none());
   m.def("fc_ce_eval", &fc_ce_eval);
   m.def("augment", &augment);
+  m.def("augment_mix", &augment_mix, py::arg("images"), py::arg("idx"), py::arg("labels"), py::arg("out"),
+        py::arg("target"), py::arg("target2"), py::arg("lam_out"), py::arg("pad"), py::arg("seed"), py::arg("salt"),
+        py::arg("mean"), py::arg("std"), py::arg("mode"), py::arg("lam"), py::arg("y0") = 0, py::arg("y1") = 0,
+        py::arg("x0") = 0, py::arg("x1") = 0);
   m.def("maxpool_fwd", &maxpool_fwd, py::arg("x"), py::arg("y"), py::arg("arg"), py::arg("k"), py::arg("s"),
         py::arg("p"), py::arg("scale") = py::none(), py::arg("shift") = py::none());
   m.def("maxpool_bwd", &maxpool_bwd);

@@ -8,6 +8,8 @@
 //   F.cross_entropy(label_smoothing=eps) with mean reduction and class-index targets):
 //     loss_row  = lse(z) - (1 - eps) * z_t - (eps / J) * sum_j z_j
 //     dlogits_j = (softmax_j - (1 - eps) * [j == t] - eps / J) / B
+//   With pair targets (the MIX training instances: Mixup / CutMix, a second class index and a
+//   per-row lambda) the one-hot target becomes lam * onehot(t1) + (1 - lam) * onehot(t2), see MixArgs.
 //   Evaluation (fc_ce_eval) is always the plain cross-entropy.
 // fc_ce_wgrad: dW[j][c] = sum_b dlogits[b][j] * x[b][c], db[j] = sum_b dlogits[b][j], and the
 //   batch-mean loss (fixed summation order -> bitwise reproducible).
@@ -37,6 +39,27 @@ struct BnIn {
 // otherwise), so the plain instances keep the argument list and the code they had before SMOOTH.
 __device__ __forceinline__ float eps_of(float e) { return e; }
 
+// Mixup / CutMix pair targets: the MIX training instances are the ones whose trailing pack is one
+// MixArgs (SMOOTH false; eps rides inside and may be 0), so the plain and the SMOOTH instances keep
+// their names, argument lists and code.  lam is read per row from device memory: a captured graph
+// never bakes it in.  q = lam * onehot(target) + (1 - lam) * onehot(target2):
+//   loss_row  = lse(z) - (1 - eps) * (lam * z_t1 + (1 - lam) * z_t2) - (eps / J) * sum_j z_j
+//   dlogits_j = (softmax_j - (1 - eps) * (lam * [j == t1] + (1 - lam) * [j == t2]) - eps / J) / B
+struct MixArgs {
+  const long long* target2;
+  const float* lam;
+  float eps;
+};
+template <typename... T>
+struct IsMix {
+  static constexpr bool value = false;
+};
+template <>
+struct IsMix<MixArgs> {
+  static constexpr bool value = true;
+};
+__device__ __forceinline__ MixArgs mix_of(MixArgs m) { return m; }
+
 template <bool TRAIN, int MAXJ, int MAXCL, bool BNIN = false, bool SMOOTH = false, typename... Eps>
 __global__ __launch_bounds__(256) void fc_ce_rows_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ bias,
@@ -46,7 +69,9 @@ __global__ __launch_bounds__(256) void fc_ce_rows_kernel(const float* __restrict
                                                          float* __restrict__ logits_out, int B, int Cin, int J,
                                                          BnIn bn = BnIn{nullptr, nullptr, nullptr},
                                                          Eps... eps_arg) {
-  static_assert(sizeof...(Eps) == (SMOOTH ? 1 : 0) && (!SMOOTH || TRAIN), "eps: SMOOTH training instances only");
+  constexpr bool MIX = IsMix<Eps...>::value;
+  static_assert(sizeof...(Eps) == ((SMOOTH || MIX) ? 1 : 0) && (!(SMOOTH || MIX) || TRAIN) && !(SMOOTH && MIX),
+                "eps: SMOOTH training instances only; MixArgs: MIX training instances only");
   extern __shared__ float w_s[];  // [J][Cin]
   // All of the block's W loads are issued together, then the row's loads, and only then is the LDS
   // image written: one memory latency for both instead of one per 4 KB of W plus one for the row
@@ -139,6 +164,20 @@ __global__ __launch_bounds__(256) void fc_ce_rows_kernel(const float* __restrict
       if (j < J) sz += logit[j];
     lr = lse - (1.f - eps) * lt - eps / (float)J * sz;
   }
+  int t2 = 0;
+  float lam = 1.f;
+  if constexpr (MIX) {
+    const MixArgs m = mix_of(eps_arg...);
+    t2 = (int)m.target2[row];
+    lam = m.lam[row];
+    float lt2 = 0.f, sz = 0.f;
+#pragma unroll
+    for (int j = 0; j < MAXJ; ++j) {
+      if (j == t2) lt2 = logit[j];
+      if (j < J) sz += logit[j];  // ascending j (fixed order), as SMOOTH
+    }
+    lr = lse - (1.f - m.eps) * (lam * lt + (1.f - lam) * lt2) - m.eps / (float)J * sz;
+  }
   if (lane == 0) {
     loss_row[row] = lr;
     if (correct_row) correct_row[row] = (arg == t) ? 1 : 0;
@@ -156,6 +195,10 @@ __global__ __launch_bounds__(256) void fc_ce_rows_kernel(const float* __restrict
       if constexpr (SMOOTH) {
         const float eps = eps_of(eps_arg...);
         dl[j] = j < J ? (expf(logit[j] - lse) - (j == t ? 1.f - eps : 0.f) - eps / (float)J) * invB : 0.f;
+      } else if constexpr (MIX) {
+        const float eps = mix_of(eps_arg...).eps;
+        const float q = (j == t ? lam : 0.f) + (j == t2 ? 1.f - lam : 0.f);
+        dl[j] = j < J ? (expf(logit[j] - lse) - (1.f - eps) * q - eps / (float)J) * invB : 0.f;
       } else
         dl[j] = j < J ? (expf(logit[j] - lse) - (j == t ? 1.f : 0.f)) * invB : 0.f;
     }
@@ -297,15 +340,30 @@ extern "C" {
 // its weight-gradient stream (nothing on the critical path reads dW, db or the loss).
 // label_smoothing (0 <= eps < 1, checked by the caller): eps != 0 runs the SMOOTH row kernels, eps == 0
 // the plain ones; only the row kernel sees it (the weight gradient reads dlogits and loss_row).
+// target2 [B] / lam [B] (both or neither; Mixup / CutMix pair targets, see MixArgs): the MIX row kernels,
+// which take eps themselves (0 included); with both null the dispatch is the one above.
 int dpa_fc_ce_train(const float* x, const float* w, const float* b, const long long* target, float* loss_row,
                     float* dlogits, float* dx, float* dw, float* db, float* loss_out, float* loss_accum, int B,
                     int Cin, int J, hipStream_t st, const float* bn_z, const float* bn_scale, const float* bn_shift,
-                    int parts, float label_smoothing) {
+                    int parts, float label_smoothing, const long long* target2, const float* lam) {
   if (J > GEN_J || Cin > 64 * GEN_CL || Cin % 4 || (long)B * J * 4 > 48 * 1024) return -2;
+  if (!target2 != !lam) return -2;
   const bool rows = parts & 1, wg = parts & 2;
   const float eps = label_smoothing;
   if (bn_z && (!bn_scale || !bn_shift || J > 10 || Cin > 512)) return -2;
-  if (rows && eps != 0.f) {
+  if (rows && target2) {
+    const BnIn bn{bn_z, bn_scale, bn_shift};
+    const MixArgs mix{target2, lam, eps};
+    if (bn_z)
+      fc_ce_rows_kernel<true, 10, 8, true, false><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
+          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, bn, mix);
+    else if (J <= 10 && Cin <= 512)
+      fc_ce_rows_kernel<true, 10, 8, false, false><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
+          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, bn, mix);
+    else
+      fc_ce_rows_kernel<true, GEN_J, GEN_CL, false, false><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
+          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, bn, mix);
+  } else if (rows && eps != 0.f) {
     const BnIn bn{bn_z, bn_scale, bn_shift};
     if (bn_z)
       fc_ce_rows_kernel<true, 10, 8, true, true><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(

@@ -175,10 +175,19 @@ class DeviceLoader:
     """Iterates (x [n,H,W,4] fp32 NHWC, target [n] int64) batches produced on-device.
 
     The returned tensors are views of persistent buffers that the NEXT batch overwrites —
-    consume a batch before requesting the next one (the training loop does)."""
+    consume a batch before requesting the next one (the training loop does).
+
+    ``mixup`` / ``cutmix`` (a Beta(alpha, alpha) parameter, at most one of them above 0, training
+    only): every batch is mixed on the device, slot b with slot m-1-b of the batch's own m samples,
+    one lambda (and one CutMix box) per batch from ``cpu_ref.mix_params(seed, salt, ...)`` -- a
+    function of (seed, epoch, batch index), so resuming mid-epoch reproduces the stream with no new
+    state.  Iteration still yields (x, target); ``loader.mix`` is the persistent pair
+    (target2 int64 [batch_size], lam float32 [batch_size]) whose first m entries belong to the batch
+    last yielded (for ``VGGEngine.set_mix`` / ``head_ce``), or None when mixing is off."""
 
     def __init__(self, dataset: ImageSet, batch_size: int, device, sampler: Optional[ShardSampler] = None,
-                 train: bool = True, seed: int = 0, pad: int = 4, backend=None, drop_last: bool = False):
+                 train: bool = True, seed: int = 0, pad: int = 4, backend=None, drop_last: bool = False,
+                 mixup: float = 0.0, cutmix: float = 0.0):
         self.device = torch.device(device)
         self.ds = dataset.to(self.device)
         self.batch_size = batch_size
@@ -200,6 +209,17 @@ class DeviceLoader:
         self.x = torch.zeros(batch_size, hw, hw, 4, device=self.device)
         self.t = torch.zeros(batch_size, dtype=torch.int64, device=self.device)
         self._idx = None
+        self.mixup, self.cutmix = float(mixup), float(cutmix)
+        if self.mixup < 0 or self.cutmix < 0 or self.mixup != self.mixup or self.cutmix != self.cutmix:
+            raise ValueError(f"mixup / cutmix must be >= 0, got {mixup!r} / {cutmix!r}")
+        if self.mixup > 0 and self.cutmix > 0:
+            raise ValueError("mixup and cutmix are mutually exclusive")
+        if (self.mixup > 0 or self.cutmix > 0) and not train:
+            raise ValueError("mixup / cutmix apply to training batches only")
+        self.mix = None
+        if self.mixup > 0 or self.cutmix > 0:
+            self.mix = (torch.zeros(batch_size, dtype=torch.int64, device=self.device),
+                        torch.ones(batch_size, dtype=torch.float32, device=self.device))
 
     def set_epoch(self, epoch: int):
         self.epoch = epoch
@@ -235,6 +255,15 @@ class DeviceLoader:
             if self.drop_last and m < self.batch_size:
                 break
             salt = (self.epoch * 1_000_003 + b) & 0x7FFFFFFFFFFF
-            self.K.augment(self.ds.images, bi, self.ds.labels, self.x[:m], self.t[:m], self.pad, self.train,
-                           self.seed, salt, MEAN, STD)
+            if self.mix is None:
+                self.K.augment(self.ds.images, bi, self.ds.labels, self.x[:m], self.t[:m], self.pad, self.train,
+                               self.seed, salt, MEAN, STD)
+            else:
+                from ..ops.cpu_ref import CUTMIX, MIXUP, mix_params
+
+                mode, alpha = (CUTMIX, self.cutmix) if self.cutmix > 0 else (MIXUP, self.mixup)
+                hs, ws = self.ds.images.shape[1], self.ds.images.shape[2]
+                lam, y0, y1, x0, x1 = mix_params(self.seed, salt, mode, alpha, hs, ws)
+                self.K.augment_mix(self.ds.images, bi, self.ds.labels, self.x[:m], self.t[:m], self.mix[0][:m],
+                                   self.mix[1][:m], self.pad, self.seed, salt, MEAN, STD, mode, lam, y0, y1, x0, x1)
             yield self.x[:m], self.t[:m]

@@ -203,6 +203,7 @@ class VGGEngine:
                                      else os.environ.get("DPA_LABEL_SMOOTHING", "0"))
         if not 0.0 <= self.label_smoothing < 1.0:
             raise ValueError(f"label_smoothing must be in [0, 1), got {self.label_smoothing}")
+        self._mix = None  # (target2, lam) of the training batches: set_mix
         dev = self.device
         L = self.spec.convs
         entries = []
@@ -723,6 +724,25 @@ class VGGEngine:
         """Where bn_apply of layer i writes: bf16 planes if layer i+1 consumes planes, else fp32."""
         return self.a3[i][:, :n] if self.a3[i] is not None else self.a[i][:n]
 
+    def set_mix(self, target2: Optional[torch.Tensor], lam: Optional[torch.Tensor]) -> None:
+        """Mixup / CutMix pair targets of the training loss: persistent buffers (a DeviceLoader's
+        ``loader.mix``) target2 int64 [>= batch] and lam float32 [>= batch] on the engine's device, whose
+        first n entries belong to the batch of n given to ``forward_backward``.  The head kernel reads
+        them (lam per row) on the device, so a captured step follows them.  ``None, None`` clears the
+        mix: the step then runs exactly the kernels it ran before.  Evaluation never sees it.  Set it
+        before a ``GraphedStep`` captures (``recapture()`` after changing the buffers)."""
+        if (target2 is None) != (lam is None):
+            raise ValueError("target2 and lam must be given together")
+        if target2 is None:
+            self._mix = None
+            return
+        if target2.dtype != torch.int64 or lam.dtype != torch.float32 or target2.dim() != 1 or lam.dim() != 1:
+            raise ValueError("set_mix: target2 must be int64 [B], lam float32 [B]")
+        dev = self.params.flat.device
+        if target2.device != dev or lam.device != dev:
+            raise ValueError(f"set_mix: target2 and lam must be on {self.device}")
+        self._mix = (target2, lam)
+
     # ------------------------------------------------------------------ training step
     def forward_backward(self, x: torch.Tensor, target: torch.Tensor,
                          grad_ready: Optional[Callable[[List[str]], None]] = None,
@@ -812,6 +832,10 @@ class VGGEngine:
                      self.g[-1][:n].view(n, -1), G["fc1.weight"], G["fc1.bias"], self.loss, self.loss_accum)
         # label smoothing: an argument of the row kernel only (parts=2 below reads dlogits / loss_row)
         smooth = {"label_smoothing": self.label_smoothing} if self.label_smoothing else {}
+        if self._mix is not None:  # pair targets: likewise the row kernel only
+            if self._mix[0].numel() < n or self._mix[1].numel() < n:
+                raise ValueError(f"set_mix buffers hold fewer than the batch's {n} rows")
+            smooth.update(target2=self._mix[0][:n], lam=self._mix[1][:n])
         K.fc_ce_train(*head_args, **bn_in, **({"parts": 1} if head_side else {}), **smooth)
         if grad_ready is not None and not head_side:
             grad_ready(["fc1.weight", "fc1.bias"])

@@ -100,13 +100,14 @@ class ResNet(nn.Module):
         x = self.bn1(self.conv1(x), pool=(mp.k, mp.stride, mp.padding))  # BN + ReLU + max-pool, one pass on GPU
         return self.layer4(self.layer3(self.layer2(self.layer1(x))))
 
-    def forward(self, x, target=None):
-        """Logits, or with ``target`` the batch-mean (label-smoothed) cross-entropy through the fused head."""
+    def forward(self, x, target=None, target2=None, lam=None):
+        """Logits, or with ``target`` the batch-mean (label-smoothed) cross-entropy through the fused head;
+        ``target2`` / ``lam`` [N] (both or neither): Mixup / CutMix pair targets (``Fn.head_ce``)."""
         if self.training:
             Fn.clear_deferred()
         f = self.features(x)
         if target is not None:
-            return Fn.head_ce(f, self.fc.weight, self.fc.bias, target, self.label_smoothing)
+            return Fn.head_ce(f, self.fc.weight, self.fc.bias, target, self.label_smoothing, target2, lam)
         return Fn.head_logits(f, self.fc.weight, self.fc.bias)
 
 

@@ -242,28 +242,45 @@ def bn_bwd_wgrad0(gsrc, nsplit, g, z, scale, shift, mean, invstd, gamma, part, c
 
 # ---------------------------------------------------------------- classifier head
 def fc_ce_train(x, w, b, target, loss_row, dlogits, dx, dw, db, loss_out, loss_accum, bn_z=None, bn_scale=None,
-                bn_shift=None, label_smoothing=0.0):
+                bn_shift=None, label_smoothing=0.0, target2=None, lam=None):
     """Linear + softmax cross-entropy (mean), forward and backward (native: fc_ce.hip).  With
     label_smoothing eps (torch's F.cross_entropy(label_smoothing=eps)):
     loss_row = lse(z) - (1 - eps) z_t - (eps / J) sum_j z_j,
-    dlogits_j = (softmax_j - (1 - eps) [j == t] - eps / J) / B."""
+    dlogits_j = (softmax_j - (1 - eps) [j == t] - eps / J) / B.
+    With pair targets (Mixup / CutMix: target2 int64 [B] and lam [B], both or neither) the one-hot
+    target is q = lam onehot(target) + (1 - lam) onehot(target2):
+    loss_row = lse(z) - (1 - eps) (lam z_t1 + (1 - lam) z_t2) - (eps / J) sum_j z_j,
+    dlogits_j = (softmax_j - (1 - eps) q_j - eps / J) / B."""
     eps = float(label_smoothing)
     if not 0.0 <= eps < 1.0:
         raise ValueError("label_smoothing must be in [0, 1)")
+    if (target2 is None) != (lam is None):
+        raise ValueError("target2 and lam must be given together")
     B = x.shape[0]
     if bn_z is not None:  # features from the last conv's z: BN + ReLU + 2x2 max-pool, written to x
         x.copy_(torch.relu(bn_z * bn_scale + bn_shift).reshape(B, 4, -1).amax(1))
     logits = x @ w.t() + b
     lse = torch.logsumexp(logits, 1)
-    lr = lse - logits.gather(1, target.view(-1, 1)).squeeze(1)
-    if eps:
-        lr = lse - (1.0 - eps) * logits.gather(1, target.view(-1, 1)).squeeze(1) - eps * logits.mean(1)
-    loss_row.copy_(lr)
     p = torch.softmax(logits, 1)
-    p[torch.arange(B), target] -= 1.0 - eps
-    if eps:
-        p -= eps / logits.shape[1]
-    p /= B
+    if target2 is not None:
+        la = lam.to(logits.dtype)
+        zt = la * logits.gather(1, target.view(-1, 1)).squeeze(1) \
+            + (1.0 - la) * logits.gather(1, target2.view(-1, 1)).squeeze(1)
+        lr = lse - (1.0 - eps) * zt - eps * logits.mean(1)
+        q = torch.zeros_like(p)
+        q[torch.arange(B), target] += la
+        q[torch.arange(B), target2] += 1.0 - la
+        p -= (1.0 - eps) * q + eps / logits.shape[1]
+        p /= B
+    else:
+        lr = lse - logits.gather(1, target.view(-1, 1)).squeeze(1)
+        if eps:
+            lr = lse - (1.0 - eps) * logits.gather(1, target.view(-1, 1)).squeeze(1) - eps * logits.mean(1)
+        p[torch.arange(B), target] -= 1.0 - eps
+        if eps:
+            p -= eps / logits.shape[1]
+        p /= B
+    loss_row.copy_(lr)
     dlogits.copy_(p.reshape(dlogits.shape))
     dx.copy_(p @ w)
     dw.copy_(p.t() @ x)
@@ -329,3 +346,62 @@ def augment(images, idx, labels, out, target, pad, train, seed, salt, mean, std)
     out.copy_(res.reshape(out.shape))
     if target is not None:
         target.copy_(labels[idx.long()])
+
+
+MIXUP, CUTMIX = 0, 1
+# The hash input of a batch's mix parameters takes the place of a slot index in aug_params' input
+# salt * 0x100000001B3 + b.  Slot indices are block indices of one launch, below 2^31; 2^32 - 1 is
+# none of them, so the mix stream never coincides with a sample's crop / flip stream of the same
+# (seed, salt).
+MIX_SLOT = 0xFFFFFFFF
+
+
+def mix_params(seed, salt, mode, alpha, Hs, Ws):
+    """(lam, y0, y1, x0, x1) of one batch's Mixup (mode 0) or CutMix (mode 1): pure Python, a
+    function of (seed, salt) alone, the one source of mix parameters for both loader backends.
+    lam0 ~ Beta(alpha, alpha).  Mixup: lam = lam0, empty box.  CutMix (the paper's rand_bbox): a
+    box of area share ~(1 - lam0) around a uniform centre, clipped to the image; lam = 1 - the
+    box's exact area share."""
+    import random
+
+    if not alpha > 0:
+        raise ValueError(f"mix alpha must be > 0, got {alpha!r}")
+    if mode not in (MIXUP, CUTMIX):
+        raise ValueError("mode must be 0 (Mixup) or 1 (CutMix)")
+    h = _mix64((seed & _MASK) ^ _mix64((salt * 0x100000001B3 + MIX_SLOT) & _MASK))
+    r = random.Random(h)
+    lam0 = r.betavariate(alpha, alpha)
+    if mode == MIXUP:
+        return lam0, 0, 0, 0, 0
+    cy, cx = r.randrange(Hs), r.randrange(Ws)
+    cut = math.sqrt(1.0 - lam0)
+    ch, cw = int(Hs * cut), int(Ws * cut)
+    y0, y1 = max(cy - ch // 2, 0), min(cy + ch // 2, Hs)
+    x0, x1 = max(cx - cw // 2, 0), min(cx + cw // 2, Ws)
+    return 1.0 - (y1 - y0) * (x1 - x0) / (Hs * Ws), y0, y1, x0, x1
+
+
+def augment_mix(images, idx, labels, out, target, target2, lam_out, pad, seed, salt, mean, std, mode, lam, y0=0,
+                y1=0, x0=0, x1=0):
+    """The training ``augment``, then slot b mixed with slot B-1-b (native: augment.hip
+    augment_mix_kernel).  Mixup: out = lam aug + (1 - lam) aug.flip(0) in fp32; CutMix: the box
+    [y0,y1) x [x0,x1) of aug.flip(0) pasted into aug.  target2 = the partners' labels, lam_out = lam."""
+    if mode not in (MIXUP, CUTMIX):
+        raise ValueError("mode must be 0 (Mixup) or 1 (CutMix)")
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError("lam must be in [0, 1]")
+    B = idx.numel()
+    Hs, Ws = images.shape[1], images.shape[2]
+    if mode == CUTMIX and not (0 <= y0 <= y1 <= Hs and 0 <= x0 <= x1 <= Ws):
+        raise ValueError("the box must lie inside the image")
+    a = torch.zeros(B, Hs, Ws, 4)
+    augment(images, idx, labels, a, target, pad, True, seed, salt, mean, std)
+    if mode == MIXUP:
+        l32 = torch.tensor(lam, dtype=torch.float32)
+        res = l32 * a + (1.0 - l32) * a.flip(0)
+    else:
+        res = a.clone()
+        res[:, y0:y1, x0:x1] = a.flip(0)[:, y0:y1, x0:x1]
+    out.copy_(res.reshape(out.shape))
+    target2.copy_(labels[idx.long()].flip(0))
+    lam_out.fill_(lam)

@@ -801,13 +801,18 @@ class HeadCE(torch.autograd.Function):
     into the optimizer arena when the DDP wrapper offers a slot (``grad_slot``)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, target, label_smoothing=0.0):
+    def forward(ctx, x, weight, bias, target, label_smoothing=0.0, target2=None, lam=None):
         N = x.shape[0]
         eps = float(label_smoothing)
         note_use(weight)
         note_use(bias)
         feat, logits = _head_fwd(x, weight, bias)
-        if not _native(x):
+        if not _native(x) and target2 is not None:  # probability targets lam onehot(t) + (1 - lam) onehot(t2)
+            la = lam.to(logits.dtype).view(-1, 1)
+            q = la * F.one_hot(target, logits.shape[1]) + (1.0 - la) * F.one_hot(target2, logits.shape[1])
+            loss = F.cross_entropy(logits, q, label_smoothing=eps)
+            dlogits = (torch.softmax(logits, 1) - (1.0 - eps) * q - eps / logits.shape[1]) / N
+        elif not _native(x):
             loss = F.cross_entropy(logits, target, label_smoothing=eps)
             p = torch.softmax(logits, 1)
             p[torch.arange(N), target] -= 1.0 - eps
@@ -819,8 +824,9 @@ class HeadCE(torch.autograd.Function):
             loss_row = torch.empty(N, device=dev, dtype=torch.float32)
             dlogits = torch.empty_like(logits)
             loss = torch.empty((), device=dev, dtype=torch.float32)
+            mix = {} if target2 is None else {"target2": target2, "lam": lam}
             _ext.require().softmax_ce(logits, target, loss_row, dlogits, None, loss.view(1), None,
-                                      label_smoothing=eps)
+                                      label_smoothing=eps, **mix)
         ctx.save_for_backward(feat, dlogits, weight)
         ctx.w_b, ctx.x_meta = (weight, bias), (x.shape, x.dtype)
         return loss
@@ -830,7 +836,7 @@ class HeadCE(torch.autograd.Function):
         feat, dlogits, weight = ctx.saved_tensors
         g = gloss.reshape(1).to(dtype=feat.dtype).contiguous()
         dx, dw, db = _head_bwd(dlogits, g, feat, weight, *ctx.w_b, *ctx.x_meta)
-        return dx, dw, db, None, None
+        return dx, dw, db, None, None, None, None
 
 
 def check_label_smoothing(label_smoothing) -> float:
@@ -842,11 +848,18 @@ def check_label_smoothing(label_smoothing) -> float:
 
 
 def head_ce(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, target: torch.Tensor,
-            label_smoothing: float = 0.0) -> torch.Tensor:
+            label_smoothing: float = 0.0, target2: Optional[torch.Tensor] = None,
+            lam: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Batch-mean cross-entropy of Linear(GAP(x)) (x NHWC bf16/fp32; weight [J,C], bias [J] fp32);
-    ``label_smoothing`` as in ``F.cross_entropy`` (mean reduction, class-index targets)."""
+    ``label_smoothing`` as in ``F.cross_entropy`` (mean reduction, class-index targets).
+    ``target2`` (int64 [N]) and ``lam`` (float32 [N]), both or neither: Mixup / CutMix pair targets,
+    ``F.cross_entropy`` with the probability targets lam onehot(target) + (1 - lam) onehot(target2)."""
     eps = check_label_smoothing(label_smoothing)
-    return HeadCE.apply(x.contiguous(), weight, bias, target.contiguous(), eps)
+    if (target2 is None) != (lam is None):
+        raise ValueError("target2 and lam must be given together")
+    if target2 is not None:
+        target2, lam = target2.contiguous(), lam.contiguous()
+    return HeadCE.apply(x.contiguous(), weight, bias, target.contiguous(), eps, target2, lam)
 
 
 def head_logits(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:

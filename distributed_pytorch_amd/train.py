@@ -191,6 +191,14 @@ def add_common_args(ap: argparse.ArgumentParser):
                    help="label smoothing of the training loss, 0 <= eps < 1, as in "
                         "nn.CrossEntropyLoss(label_smoothing=eps); the test loss stays the plain cross-entropy "
                         "(default: DPA_LABEL_SMOOTHING or 0)")
+    mx = g.add_mutually_exclusive_group()
+    mx.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
+                    help="Mixup of the training batches with lambda ~ Beta(ALPHA, ALPHA), one per batch, each "
+                         "sample paired with the batch's mirror slot; mixed on the device, the loss takes the "
+                         "pair targets (default: 0 = off)")
+    mx.add_argument("--cutmix", type=float, default=0.0, metavar="ALPHA",
+                    help="CutMix of the training batches: one box per batch of area share ~(1 - Beta(ALPHA, ALPHA)) "
+                         "pasted from the mirror slot, lambda = the exact area share kept (default: 0 = off)")
     g.add_argument("--seed", type=int, default=1)
     g.add_argument("--sampler-seed", type=int, default=0)
     g.add_argument("--data-root", default="./data")
@@ -272,10 +280,13 @@ def run(ctx: DistContext, mode: str, args):
     sampler = ShardSampler(len(train_set), num_replicas=ctx.world, rank=ctx.rank, shuffle=True,
                            seed=args.sampler_seed, drop_last=False)
     train_loader = DeviceLoader(train_set, args.batch_size, ctx.device, sampler=sampler, train=True,
-                                seed=args.seed * 7919 + ctx.rank)
+                                seed=args.seed * 7919 + ctx.rank, mixup=getattr(args, "mixup", 0.0),
+                                cutmix=getattr(args, "cutmix", 0.0))
     test_loader = DeviceLoader(test_set, args.batch_size, ctx.device, sampler=None, train=False)
     engine = build_engine(args, ctx.device)
     engine.init_parameters(seed=args.seed)
+    if train_loader.mix is not None:  # Mixup / CutMix: the training loss takes the loader's pair targets
+        engine.set_mix(*train_loader.mix)
     start_epoch, start_batch = resume(ctx, engine, mode, args, len(train_loader))
     sync = make_sync(mode, engine, ctx.comm, bucket_mb=args.bucket_mb, overlap=not args.no_overlap)
     budget = getattr(args, "stop_after_iters", None)
@@ -312,6 +323,9 @@ def run(ctx: DistContext, mode: str, args):
                 rec["test_loss"], rec["test_correct"] = res
             if engine.label_smoothing:  # train_loss is then the smoothed loss, test_loss the plain one
                 rec["label_smoothing"] = engine.label_smoothing
+            for k in ("mixup", "cutmix"):  # train_loss is then the pair-target loss of the mixed batches
+                if getattr(args, k, 0.0):
+                    rec[k] = getattr(args, k)
             if engine.whole_arena_step and engine.steps_taken > 0:  # the epoch's last step
                 ost = engine.opt_stats()
                 rec["grad_norm"], rec["clip_coef"] = ost["grad_norm"], ost["clip_coef"]
