@@ -23,6 +23,22 @@ __global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ p, co
   }
 }
 
+// The same update with the learning rate read from device memory (lr_sched.hip: the rate of a
+// schedule, written by lr_advance earlier on the step's main stream), once per thread before the
+// loop.  A sibling kernel, so sgd_flat_kernel stays the code it is; the per-element code is shared.
+template <int NP>
+__global__ __launch_bounds__(256) void sgd_flat_dlr_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ buf, long n4,
+                                                           const float* __restrict__ lrp, float momentum, float wd,
+                                                           float gscale, int first, u16* __restrict__ planes,
+                                                           long ps) {
+  const float lr = lrp[0];
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    sgd_update4<NP>(p, g, buf, i, lr, momentum, wd, gscale, 1.f, first, planes, ps);
+  }
+}
+
 // K11 — mean over W stacked copies: out[i] = (sum_w in[w*n + i]) / W   (gather mode, rank 0).
 __global__ __launch_bounds__(256) void mean_of_w_kernel(const float* __restrict__ in, float* __restrict__ out, long n,
                                                         int W) {
@@ -57,6 +73,23 @@ extern "C" int dpa_sgd_flat(float* p, const float* g, float* buf, long n, float 
     sgd_flat_kernel<1><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, planes, ps);
   else
     sgd_flat_kernel<0><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, nullptr, 0);
+  return (int)hipGetLastError();
+}
+
+// dpa_sgd_flat with the rate in device memory (lr: one float32)
+extern "C" int dpa_sgd_flat_dlr(float* p, const float* g, float* buf, long n, const float* lr, float momentum,
+                                float wd, float gscale, int first, u16* planes, long ps, int np, hipStream_t s) {
+  if (n % 4 || !lr) return -1;
+  const long n4 = n / 4;
+  const int grid = grid_for(n4, 256);
+  if (planes && np == 3)
+    sgd_flat_dlr_kernel<3><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, planes, ps);
+  else if (planes && np == 2)
+    sgd_flat_dlr_kernel<2><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, planes, ps);
+  else if (planes && np == 1)
+    sgd_flat_dlr_kernel<1><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, planes, ps);
+  else
+    sgd_flat_dlr_kernel<0><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, nullptr, 0);
   return (int)hipGetLastError();
 }
 

@@ -15,6 +15,8 @@ step is a static schedule of native kernels over persistent buffers:
             bn_bwd sum them while computing their statistics
   update    sgd_flat over the flat parameter/grad/momentum arenas (one launch); with LARS or
             gradient clipping: sqnorm_partials → lars_finalize → sgd_segmented (three launches)
+  schedule  (set_lr_schedule only) lr_advance first: the step's rate from the host-built table
+            into a device word, which the update kernels' _dlr instances read
 
 Parameters/grads/momentum are three :class:`~distributed_pytorch_amd.utils.arena.Arena` s with
 identical layout (reference ``named_parameters()`` order; conv weights stored KRSC, the first
@@ -204,6 +206,11 @@ class VGGEngine:
         if not 0.0 <= self.label_smoothing < 1.0:
             raise ValueError(f"label_smoothing must be in [0, 1), got {self.label_smoothing}")
         self._mix = None  # (target2, lam) of the training batches: set_mix
+        # learning-rate schedule (set_lr_schedule): the host-built float32 table and its spec; on the
+        # GPU also the table's device copy and the words step_dev / lr_dev, which exist only while a
+        # schedule is set.  None: the constant rate self.lr, a kernel argument.
+        self._lr_table = None
+        self.lr_spec: Optional[dict] = None
         dev = self.device
         L = self.spec.convs
         entries = []
@@ -743,6 +750,63 @@ class VGGEngine:
             raise ValueError(f"set_mix: target2 and lam must be on {self.device}")
         self._mix = (target2, lam)
 
+    def set_lr_schedule(self, table, spec: Optional[dict] = None) -> None:
+        """A learning-rate schedule as a float32 table indexed by the global update step
+        (``schedule.lr_table``; steps at or past its end hold the last value).  ``spec``: the dict
+        that describes it (default: the table's own), kept as ``lr_spec`` for checkpoints and the
+        metrics line.  ``None`` clears the schedule: the step then runs exactly the launches it ran
+        before, at the constant rate ``self.lr``.
+
+        On the GPU the table is uploaded once; every ``forward_backward`` starts with ``lr_advance``
+        (one wave), which writes the step's rate into ``lr_dev``, and the update kernels read it
+        there -- so a captured step follows the schedule from replay to replay.  The position is
+        ``steps_taken``: nothing else is saved or restored."""
+        if table is None:
+            self._lr_table = self.lr_spec = None
+            for a in ("table_dev", "step_dev", "lr_dev"):
+                if hasattr(self, a):
+                    delattr(self, a)
+            return
+        from .schedule import as_table, table_spec
+
+        tab = as_table(table)
+        self.lr_spec = table_spec(table, spec)
+        self._lr_table = tab
+        self._lr_last = float(tab[0])  # CPU backend: the rate and the counter as host values
+        self._lr_pos = 0
+        if self.K is not cpu_ref:
+            dev = self.params.flat.device
+            self.table_dev = torch.from_numpy(tab.copy()).to(dev)
+            self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.lr_dev = self.table_dev[:1].clone()
+
+    def _lr_advance(self):
+        """First launch of a scheduled step on the main stream: lr_dev = table[min(step, T - 1)].
+        Eager: the step is the host's count (steps_taken stays the single truth, so whatever
+        restores it -- a checkpoint, the comm tuner -- moves the schedule with it).  Under capture:
+        the device counter, so that every replay advances by itself (GraphedStep seeds it)."""
+        tab = self._lr_table
+        if self.K is cpu_ref:
+            self._lr_last = float(tab[min(self.steps_taken, len(tab) - 1)])
+            self._lr_pos = self.steps_taken + 1
+            return
+        self.K.lr_advance(self.table_dev, self.step_dev, self.lr_dev, self.steps_taken,
+                          torch.cuda.is_current_stream_capturing())
+
+    def current_lr(self) -> float:
+        """The learning rate of the most recent step (synchronises); ``self.lr`` without a schedule.
+        Before the first step of a schedule: its first value."""
+        if self._lr_table is None:
+            return self.lr
+        return self._lr_last if self.K is cpu_ref else float(self.lr_dev.item())
+
+    def lr_position(self) -> int:
+        """The schedule's step counter (on the GPU the device word; synchronises): the number of
+        scheduled steps begun, counted from the global step 0."""
+        if self._lr_table is None:
+            raise ValueError("lr_position: no learning-rate schedule is set")
+        return self._lr_pos if self.K is cpu_ref else int(self.step_dev.item())
+
     # ------------------------------------------------------------------ training step
     def forward_backward(self, x: torch.Tensor, target: torch.Tensor,
                          grad_ready: Optional[Callable[[List[str]], None]] = None,
@@ -765,6 +829,16 @@ class VGGEngine:
         K, P, G = self.K, self.params, self.grads
         n = x.shape[0]
         L = self.spec.convs
+        if self._lr_table is not None:
+            # The step's rate, before anything else on the main stream.  Every update of this step
+            # that reads lr_dev is ordered behind it: the whole-arena update runs on the main stream
+            # after backward; a per-bucket update (DPA_FUSED_STEP=1) runs on the wgrad or comm
+            # stream only after that stream has waited for main-stream work of this step (the
+            # sync's join / comm region, or the start signal of a BN backward of this step); ZeRO-1
+            # shard updates run on the main stream after finish().  And it overwrites lr_dev only
+            # after the previous step's readers: the main stream joined the wgrad and comm streams
+            # (end of backward, sync.finish()) before that step's update returned.
+            self._lr_advance()
         buffers_wait = pre_forward() if pre_forward is not None else None
         epoch = 0
         if self.ksignal and not torch.cuda.is_current_stream_capturing():
@@ -1001,6 +1075,10 @@ class VGGEngine:
         self._sgd(grad_scale, offset, count, self.steps_taken == 0 if first is None else first)
 
     def _sgd(self, grad_scale: float, offset: int, count: int, first: bool):
+        # a schedule's rate: on the GPU the device word lr_dev (the _dlr entry points read it), on the
+        # CPU backend the table's value for this step, handed to the same functions as self.lr
+        dlr = self._lr_table is not None and self.K is not cpu_ref
+        lr = self.lr if self._lr_table is None else self._lr_last
         if self.whole_arena_step:
             n = self.params.flat.numel()
             if offset != 0 or (count >= 0 and count != n):
@@ -1010,10 +1088,18 @@ class VGGEngine:
             K.sqnorm_partials(p, g, self._opt_bmap, self._opt_partials, self._opt_segs.shape[0])
             K.lars_finalize(self._opt_partials, self._opt_segs, self._opt_table, self._opt_stats, grad_scale,
                             self.clip_grad_norm, self.trust_coef, self.weight_decay, self.lars_eps)
-            K.sgd_segmented(p, g, self.mom.flat, self._opt_bmap, self._opt_table, self.lr, self.momentum,
-                            self.weight_decay, first, self.wplanes)
+            if dlr:
+                K.sgd_segmented_dlr(p, g, self.mom.flat, self._opt_bmap, self._opt_table, self.lr_dev, self.momentum,
+                                    self.weight_decay, first, self.wplanes)
+            else:
+                K.sgd_segmented(p, g, self.mom.flat, self._opt_bmap, self._opt_table, lr, self.momentum,
+                                self.weight_decay, first, self.wplanes)
             return
-        self.K.sgd_flat(self.params.flat, self.grads.flat, self.mom.flat, self.lr, self.momentum, self.weight_decay,
+        if dlr:
+            self.K.sgd_flat_dlr(self.params.flat, self.grads.flat, self.mom.flat, self.lr_dev, self.momentum,
+                                self.weight_decay, grad_scale, first, offset, count, self.wplanes)
+            return
+        self.K.sgd_flat(self.params.flat, self.grads.flat, self.mom.flat, lr, self.momentum, self.weight_decay,
                         grad_scale, first, offset, count, self.wplanes)
 
     def opt_stats(self) -> dict:

@@ -10,8 +10,14 @@ Scope (by construction, checked at construction time):
 * single-rank communicator: with a real communicator the collectives, their watchdog events and
   the DDP buffer broadcast stay eager (``ValueError``);
 * full batches only (a partial last batch runs the eager step);
-* the learning rate / momentum / weight decay are baked into the graph: ``recapture()`` after
-  changing them.
+* momentum, weight decay and a constant learning rate (``engine.lr``) are kernel arguments baked
+  into the graph: ``recapture()`` after changing them.  A learning-rate SCHEDULE
+  (``engine.set_lr_schedule``) is not baked in: the captured ``lr_advance`` reads and advances a
+  device counter and the update kernels read the rate from device memory, so every replay trains
+  at its own step's rate.  The counter is seeded with ``engine.steps_taken`` right before the
+  capture (a resumed run past the warm-up count captures on its first step), and an eager step
+  between replays (a partial batch) re-seeds it from the host count, so the two forms interleave
+  freely.  Set or clear the schedule before the capture (``recapture()`` afterwards).
 The first ``warmup`` steps run eagerly (the first SGD step initialises the momentum buffers with
 a different kernel argument, and the split-K workspaces are allocated lazily).
 """
@@ -62,6 +68,10 @@ class GraphedStep:
             self._body(x, t)
         else:
             torch.cuda.synchronize(e.device)
+            if getattr(e, "lr_spec", None) is not None:
+                # the captured lr_advance counts on the device: start it at the host's step count
+                # (the capture itself runs nothing; the replay below performs step steps_taken)
+                e.step_dev.fill_(e.steps_taken)
             g = torch.cuda.CUDAGraph()
             try:
                 with torch.cuda.graph(g):

@@ -101,6 +101,24 @@ def sgd_segmented(p, g, buf, bmap, table, lr, momentum, wd, first, planes=None):
         planes[:, cov] = pl[:, cov]
 
 
+def lr_advance(table, step, lr, host_pos, from_device):
+    """kernels/lr_sched.hip: lr[0] = table[min(pos, T - 1)], step[0] = pos + 1, with pos the
+    counter's value (from_device) or host_pos."""
+    pos = int(step[0]) if from_device else int(host_pos)
+    lr[0] = table[min(max(pos, 0), table.numel() - 1)]
+    step[0] = pos + 1
+
+
+def sgd_flat_dlr(p, g, buf, lr, momentum, wd, gscale, first, offset=0, count=-1, planes=None):
+    """sgd_flat with the rate read from the 1-element float32 tensor lr."""
+    sgd_flat(p, g, buf, float(lr[0]), momentum, wd, gscale, first, offset, count, planes)
+
+
+def sgd_segmented_dlr(p, g, buf, bmap, table, lr, momentum, wd, first, planes=None):
+    """sgd_segmented with the rate read from the 1-element float32 tensor lr."""
+    sgd_segmented(p, g, buf, bmap, table, float(lr[0]), momentum, wd, first, planes)
+
+
 def split_bf16(x, np_):
     """fp32 -> [np_, *x.shape] bf16 planes (round-to-nearest-even), the HIP split's semantics."""
     out, r = [], x.float()

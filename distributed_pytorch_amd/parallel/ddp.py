@@ -259,14 +259,30 @@ class FlatSGD:
     ``trust_coef`` (not None): LARS, a trust ratio on every parameter of rank >= 2;
     ``clip_grad_norm`` > 0: global-norm gradient clipping.  Either makes the step the three
     launches of kernels/lars.hip over the wrapper's parameters as segments (fp32 arena on the GPU;
-    anything else runs ops/cpu_ref)."""
+    anything else runs ops/cpu_ref).
+
+    ``schedule``: a learning-rate table (``schedule.lr_table``) indexed by ``self.steps``; ``lr`` is
+    then unused.  On the GPU ``step()`` starts with ``lr_advance`` (kernels/lr_sched.hip) and the
+    update reads the rate from device memory, so a captured ``step()`` follows the schedule; the
+    oracle path hands the table's value to the same reference functions."""
 
     def __init__(self, ddp: DistributedDataParallel, lr: float, momentum: float = 0.0, weight_decay: float = 0.0,
-                 trust_coef: Optional[float] = None, clip_grad_norm: Optional[float] = None, lars_eps: float = 1e-9):
+                 trust_coef: Optional[float] = None, clip_grad_norm: Optional[float] = None, lars_eps: float = 1e-9,
+                 schedule=None):
         self.ddp = ddp
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.buf = torch.zeros_like(ddp.flat_params)
         self.steps = 0
+        self._lr_table = self.lr_spec = None
+        if schedule is not None:
+            from ..schedule import as_table, table_spec
+
+            p = ddp.flat_params
+            self._lr_table, self.lr_spec = as_table(schedule), table_spec(schedule)
+            if p.is_cuda and p.dtype == torch.float32:
+                self.table_dev = torch.from_numpy(self._lr_table.copy()).to(p.device)
+                self.step_dev = torch.zeros(1, dtype=torch.int64, device=p.device)
+                self.lr_dev = self.table_dev[:1].clone()
         self.trust_coef, self.lars_eps = trust_coef, lars_eps
         self.clip_grad_norm = float(clip_grad_norm or 0.0)
         self.segmented = trust_coef is not None or self.clip_grad_norm > 0
@@ -300,20 +316,46 @@ class FlatSGD:
     @torch.no_grad()
     def step(self, grad_scale: float = 1.0):
         p, g = self.ddp.flat_params, self.ddp.flat_grads
+        lr, dlr = self.lr, False
+        if self._lr_table is not None:
+            dlr = hasattr(self, "lr_dev")
+            if dlr:  # first launch of the step: the rate that the update kernel below reads
+                from .. import _ext
+
+                _ext.require().lr_advance(self.table_dev, self.step_dev, self.lr_dev, self.steps,
+                                          torch.cuda.is_current_stream_capturing())
+            else:
+                lr = float(self._lr_table[min(self.steps, len(self._lr_table) - 1)])
         if self.segmented:
             K = self._backend()
             K.sqnorm_partials(p, g, self._bmap, self._partials, self._segs.shape[0])
             K.lars_finalize(self._partials, self._segs, self._table, self._stats, grad_scale, self.clip_grad_norm,
                             self.trust_coef or 0.0, self.weight_decay, self.lars_eps)
-            K.sgd_segmented(p, g, self.buf, self._bmap, self._table, self.lr, self.momentum, self.weight_decay,
-                            self.steps == 0, self.ddp.weight_planes if self._native else None)
+            if dlr and self._native:
+                K.sgd_segmented_dlr(p, g, self.buf, self._bmap, self._table, self.lr_dev, self.momentum,
+                                    self.weight_decay, self.steps == 0, self.ddp.weight_planes)
+            else:
+                K.sgd_segmented(p, g, self.buf, self._bmap, self._table, lr, self.momentum, self.weight_decay,
+                                self.steps == 0, self.ddp.weight_planes if self._native else None)
         elif p.is_cuda:
             from .. import _ext
 
-            _ext.require().sgd_flat(p, g, self.buf, self.lr, self.momentum, self.weight_decay, grad_scale,
-                                    self.steps == 0, 0, -1, self.ddp.weight_planes)
+            if dlr:
+                _ext.require().sgd_flat_dlr(p, g, self.buf, self.lr_dev, self.momentum, self.weight_decay, grad_scale,
+                                            self.steps == 0, 0, -1, self.ddp.weight_planes)
+            else:
+                _ext.require().sgd_flat(p, g, self.buf, lr, self.momentum, self.weight_decay, grad_scale,
+                                        self.steps == 0, 0, -1, self.ddp.weight_planes)
         else:
             from ..ops import cpu_ref
 
-            cpu_ref.sgd_flat(p, g, self.buf, self.lr, self.momentum, self.weight_decay, grad_scale, self.steps == 0)
+            cpu_ref.sgd_flat(p, g, self.buf, lr, self.momentum, self.weight_decay, grad_scale, self.steps == 0)
         self.steps += 1
+
+    def current_lr(self) -> float:
+        """The rate of the most recent step (synchronises); ``self.lr`` without a schedule."""
+        if self._lr_table is None:
+            return self.lr
+        if hasattr(self, "lr_dev"):
+            return float(self.lr_dev.item())
+        return float(self._lr_table[min(max(self.steps - 1, 0), len(self._lr_table) - 1)])

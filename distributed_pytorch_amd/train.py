@@ -27,6 +27,7 @@ from .data import DeviceLoader, ShardSampler, get_datasets
 from .engine import VGGEngine
 from .graph_step import GraphedStep
 from .parallel import DistContext, env_dict, init_cli, init_env, init_single, make_sync
+from .schedule import table_from_args
 from .utils import checkpoint
 from .utils.profiling import enable_tracing, trace_range
 
@@ -199,6 +200,19 @@ def add_common_args(ap: argparse.ArgumentParser):
     mx.add_argument("--cutmix", type=float, default=0.0, metavar="ALPHA",
                     help="CutMix of the training batches: one box per batch of area share ~(1 - Beta(ALPHA, ALPHA)) "
                          "pasted from the mirror slot, lambda = the exact area share kept (default: 0 = off)")
+    g.add_argument("--lr-schedule", default=None, choices=["constant", "poly", "cosine", "step"],
+                   help="learning-rate decay after the warmup, per iteration over epochs x iterations-per-epoch "
+                        "steps (schedule.py); the rate then lives on the device, so --graph follows it "
+                        "(default: none, the constant --lr as a kernel argument)")
+    g.add_argument("--warmup-iters", type=int, default=0,
+                   help="linear warmup over this many iterations from --warmup-factor x --lr; alone it means "
+                        "warmup followed by the constant rate")
+    g.add_argument("--warmup-factor", type=float, default=0.1)
+    g.add_argument("--lr-power", type=float, default=2.0, help="poly: exponent (1 = linear; LARS paper: 2)")
+    g.add_argument("--lr-end", type=float, default=0.0, help="poly / cosine: the final rate")
+    g.add_argument("--lr-milestones", default="", metavar="E1,E2,...",
+                   help="step: the epochs at which the rate is multiplied by --lr-gamma")
+    g.add_argument("--lr-gamma", type=float, default=0.1)
     g.add_argument("--seed", type=int, default=1)
     g.add_argument("--sampler-seed", type=int, default=0)
     g.add_argument("--data-root", default="./data")
@@ -287,6 +301,11 @@ def run(ctx: DistContext, mode: str, args):
     engine.init_parameters(seed=args.seed)
     if train_loader.mix is not None:  # Mixup / CutMix: the training loss takes the loader's pair targets
         engine.set_mix(*train_loader.mix)
+    # the schedule covers epochs x (this rank's iterations per epoch); set before resume(), which
+    # checks the checkpoint's schedule against it and restores its position (steps_taken)
+    table = table_from_args(args, min(len(train_loader), args.max_iters or len(train_loader)))
+    if table is not None:
+        engine.set_lr_schedule(table)
     start_epoch, start_batch = resume(ctx, engine, mode, args, len(train_loader))
     sync = make_sync(mode, engine, ctx.comm, bucket_mb=args.bucket_mb, overlap=not args.no_overlap)
     budget = getattr(args, "stop_after_iters", None)
@@ -326,6 +345,8 @@ def run(ctx: DistContext, mode: str, args):
             for k in ("mixup", "cutmix"):  # train_loss is then the pair-target loss of the mixed batches
                 if getattr(args, k, 0.0):
                     rec[k] = getattr(args, k)
+            if engine.lr_spec is not None:  # the rate of the epoch's last step
+                rec["lr"], rec["lr_schedule"] = engine.current_lr(), engine.lr_spec
             if engine.whole_arena_step and engine.steps_taken > 0:  # the epoch's last step
                 ost = engine.opt_stats()
                 rec["grad_norm"], rec["clip_coef"] = ost["grad_norm"], ost["clip_coef"]

@@ -7,6 +7,8 @@ Layout: ``<dir>/rank{R}.pt`` holding
      "optimizer": torch.optim.SGD state_dict (momentum_buffer per param),
      "epoch": int, "batch_idx": int (next batch to run), "sampler_seed": int,
      "world": int, "mode": str, "steps_taken": int, "rng": torch CPU RNG state}
+    + "lr_schedule": the schedule's spec dict, only when the engine has a learning-rate schedule
+      (its position is ``steps_taken``; ``optimizer`` keeps the base rate)
 
 ``model`` loads straight into ``model.VGG11().load_state_dict`` (after stripping ``module.``).
 Loading uses ``torch.load(weights_only=True)`` — nothing in the file is executed.
@@ -17,6 +19,8 @@ Resume safety:
   weights and optimizer state anyway and restarts the saved epoch at batch 0.  A rank with no file
   of its own (the world grew: ranks >= the old world size) then loads the lowest-numbered rank's
   file — after ``prepare_checkpoint`` every rank saved identical parameters and full momentum;
+* a checkpoint whose learning-rate schedule differs from the engine's (another spec, or a schedule
+  on one side only) is refused: the saved step count would index another table;
 * ``agree`` (after every rank loaded) checks that all ranks resume from the same
   (epoch, batch_idx, steps_taken) — ranks holding checkpoints of different iterations (a crash
   between two ``--checkpoint-every`` writes) or a rank without one would otherwise pair gradients
@@ -53,6 +57,9 @@ def save(ckpt_dir: str, rank: int, engine, epoch: int, batch_idx: int, sampler_s
         "steps_taken": int(engine.steps_taken),
         "rng": torch.get_rng_state(),
     }
+    spec = getattr(engine, "lr_spec", None)
+    if spec is not None:  # a learning-rate schedule: its position is steps_taken, nothing else is state
+        obj["lr_schedule"] = spec
     p = path_for(ckpt_dir, rank)
     tmp = p + ".tmp"
     torch.save(obj, tmp)
@@ -92,6 +99,11 @@ def load(ckpt_dir: str, rank: int, engine, map_location="cpu", world: Optional[i
                                  f"the epoch at batch 0.")
         warnings.warn(f"resuming {p} across a topology change ({what}): restarting epoch {obj['epoch']} at batch 0")
         obj = dict(obj, batch_idx=0)
+    saved_s, cur_s = obj.get("lr_schedule"), getattr(engine, "lr_spec", None)
+    if saved_s != cur_s:
+        raise ResumeMismatch(f"{p} was written with the learning-rate schedule {saved_s}, this run has {cur_s}: "
+                             "the saved step count would index another schedule. Resume with the schedule options "
+                             "of the run that wrote the checkpoint.")
     engine.load_state_dict(obj["model"])
     engine.load_optimizer_state_dict(obj["optimizer"])
     if "steps_taken" in obj:
