@@ -4,28 +4,12 @@
 #include <c10/hip/HIPCachingAllocator.h>
 #include <torch/extension.h>
 
+#include "kernels/optim_api.h"
 #include "runtime/ipc_comm.h"
 #include "runtime/rccl_comm.h"
 #include "runtime/tcp_store.h"
 
 extern "C" {
-int dpa_sgd_flat(float* p, const float* g, float* buf, long n, float lr, float momentum, float wd, float gscale,
-                 int first, unsigned short* planes, long ps, int np, hipStream_t s);
-int dpa_opt_chunk();
-int dpa_opt_max_segments();
-int dpa_sqnorm_partials(const float* p, const float* g, const long* bmap, long nblocks, long n, int nseg,
-                        double* partials, hipStream_t s);
-int dpa_lars_finalize(const double* partials, long nblocks, const long* segs, int nseg, float* table, double* stats,
-                      double gs, double max_norm, double trust, double wd, double eps, hipStream_t s);
-int dpa_sgd_segmented(float* p, const float* g, float* buf, const long* bmap, long nblocks, long n, int nseg,
-                      const float* table, float lr, float momentum, float wd, int first, unsigned short* planes,
-                      long ps, int np, hipStream_t s);
-int dpa_lr_advance(const float* table, long T, long* step, float* lr, long host_pos, int from_device, hipStream_t s);
-int dpa_sgd_flat_dlr(float* p, const float* g, float* buf, long n, const float* lr, float momentum, float wd,
-                     float gscale, int first, unsigned short* planes, long ps, int np, hipStream_t s);
-int dpa_sgd_segmented_dlr(float* p, const float* g, float* buf, const long* bmap, long nblocks, long n, int nseg,
-                          const float* table, const float* lr, float momentum, float wd, int first,
-                          unsigned short* planes, long ps, int np, hipStream_t s);
 int dpa_spin(long long usec, int* done, hipStream_t s);
 int dpa_mean_of_w(const float* in, float* out, long n, int W, hipStream_t s);
 int dpa_add_inplace(void* out, const void* add, long n, int bf, hipStream_t s);
@@ -202,29 +186,58 @@ const long long* mix_targets(const OptT& target2, const OptT& lam, int64_t B, co
 }
 
 // ---------------- optimizer / elementwise ----------------
+// one float32 word on the arenas' device holding the step's learning rate
+const float* lr_word(const Tensor& lr, const Tensor& like, const char* what) {
+  need(lr, "lr");
+  TORCH_CHECK(lr.numel() == 1, what, ": lr must be a 1-element float32 GPU tensor");
+  TORCH_CHECK(lr.device() == like.device(), what, ": lr must be on the arenas' device");
+  return fp(lr);
+}
+
+// the rate of sgd_flat / sgd_segmented: a Python float (*lr; returns null), or an lr_word that the
+// kernel reads (returns its pointer)
+using Rate = std::variant<Tensor, double>;
+const float* opt_rate(const Rate& rate, const Tensor& like, const char* what, float* lr) {
+  *lr = 0.f;
+  if (const Tensor* t = std::get_if<Tensor>(&rate)) return lr_word(*t, like, what);
+  *lr = (float)std::get<double>(rate);
+  return nullptr;
+}
+
+// planes of sgd_flat / sgd_segmented: pointer to plane 0 (null: none), plane stride and count
+unsigned short* opt_planes(const OptT& planes, const Tensor& p, const char* what, long* ps, int* np) {
+  *ps = 0;
+  *np = 0;
+  if (!(planes.has_value() && planes->defined())) return nullptr;
+  const Tensor& t = *planes;
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 2 && t.size(1) == p.numel() &&
+                  ((t.scalar_type() == at::kBFloat16 && (t.size(0) == 1 || t.size(0) == 3)) ||
+                   (t.scalar_type() == at::kHalf && t.size(0) == 2)),
+              what, ": planes must be contiguous bfloat16 [1 or 3, p.numel()] or float16 [2, p.numel()]");
+  *np = (int)t.size(0);
+  *ps = t.stride(0);
+  return reinterpret_cast<unsigned short*>(t.data_ptr());
+}
+
 // planes (optional): bf16 [NP, p.numel()] operand planes of the whole arena, refreshed in the same pass
-void sgd_flat(Tensor p, Tensor g, Tensor buf, double lr, double momentum, double wd, double gscale, bool first,
+void sgd_flat(Tensor p, Tensor g, Tensor buf, Rate lr, double momentum, double wd, double gscale, bool first,
               int64_t offset, int64_t count, OptT planes) {
   need(p, "p");
   need(g, "g");
   need(buf, "buf");
+  float lrv;
+  const float* lrd = opt_rate(lr, p, "sgd_flat", &lrv);
+  TORCH_CHECK(offset >= 0, "sgd_flat: offset must be >= 0");
   if (count < 0) count = p.numel() - offset;
   TORCH_CHECK(offset % 4 == 0 && count % 4 == 0, "sgd_flat: offset/count must be multiples of 4");
-  TORCH_CHECK(offset + count <= p.numel() && p.numel() == g.numel() && p.numel() == buf.numel(), "sgd_flat sizes");
-  unsigned short* pl = nullptr;
-  long ps = 0;
-  int np = 0;
-  if (planes.has_value() && planes->defined()) {
-    const Tensor& t = *planes;
-    TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 2 && t.size(1) == p.numel() &&
-                    ((t.scalar_type() == at::kBFloat16 && (t.size(0) == 1 || t.size(0) == 3)) ||
-                     (t.scalar_type() == at::kHalf && t.size(0) == 2)),
-                "sgd_flat: planes must be contiguous bfloat16 [1 or 3, p.numel()] or float16 [2, p.numel()]");
-    np = t.size(0);
-    ps = t.stride(0);
-    pl = reinterpret_cast<unsigned short*>(t.data_ptr()) + offset;
-  }
-  chk(dpa_sgd_flat(fp(p) + offset, fp(g) + offset, fp(buf) + offset, count, (float)lr, (float)momentum, (float)wd,
+  TORCH_CHECK(count >= 0 && offset <= p.numel() && count <= p.numel() - offset && p.numel() == g.numel() &&
+                  p.numel() == buf.numel(),
+              "sgd_flat sizes");
+  long ps;
+  int np;
+  unsigned short* pl = opt_planes(planes, p, "sgd_flat", &ps, &np);
+  if (pl) pl += offset;
+  chk(dpa_sgd_flat(fp(p) + offset, fp(g) + offset, fp(buf) + offset, count, lrv, lrd, (float)momentum, (float)wd,
                    (float)gscale, first ? 1 : 0, pl, ps, np, cur_stream()),
       "sgd_flat");
 }
@@ -277,57 +290,26 @@ void lars_finalize(Tensor partials, Tensor segs, Tensor table, Tensor stats, dou
 }
 
 // the update of sgd_flat over the whole arena, chunk by chunk, with table's ratios and multiplier
-void sgd_segmented(Tensor p, Tensor g, Tensor buf, Tensor bmap, Tensor table, double lr, double momentum, double wd,
+void sgd_segmented(Tensor p, Tensor g, Tensor buf, Tensor bmap, Tensor table, Rate lr, double momentum, double wd,
                    bool first, OptT planes) {
   opt_arenas(p, g, "sgd_segmented");
   need(buf, "buf");
   TORCH_CHECK(buf.numel() == p.numel(), "sgd_segmented sizes");
   const long* bm = opt_table(bmap, "bmap");
   need(table, "table");
+  float lrv;
+  const float* lrd = opt_rate(lr, p, "sgd_segmented", &lrv);
   const int64_t nseg = table.numel() - 1;
   TORCH_CHECK(nseg >= 1 && nseg <= dpa_opt_max_segments(), "sgd_segmented: table must be float32 [nseg + 1]");
-  unsigned short* pl = nullptr;
-  long ps = 0;
-  int np = 0;
-  if (planes.has_value() && planes->defined()) {
-    const Tensor& t = *planes;
-    TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 2 && t.size(1) == p.numel() &&
-                    ((t.scalar_type() == at::kBFloat16 && (t.size(0) == 1 || t.size(0) == 3)) ||
-                     (t.scalar_type() == at::kHalf && t.size(0) == 2)),
-                "sgd_segmented: planes must be contiguous bfloat16 [1 or 3, p.numel()] or float16 [2, p.numel()]");
-    np = t.size(0);
-    ps = t.stride(0);
-    pl = reinterpret_cast<unsigned short*>(t.data_ptr());
-  }
-  chk(dpa_sgd_segmented(fp(p), fp(g), fp(buf), bm, bmap.size(0), p.numel(), (int)nseg, fp(table), (float)lr,
+  long ps;
+  int np;
+  unsigned short* pl = opt_planes(planes, p, "sgd_segmented", &ps, &np);
+  chk(dpa_sgd_segmented(fp(p), fp(g), fp(buf), bm, bmap.size(0), p.numel(), (int)nseg, fp(table), lrv, lrd,
                         (float)momentum, (float)wd, first ? 1 : 0, pl, ps, np, cur_stream()),
       "sgd_segmented");
 }
 
 // ---- learning-rate schedules (kernels/lr_sched.hip): the rate lives in device memory ----
-// one float32 word on the arenas' device holding the step's learning rate
-const float* lr_word(const Tensor& lr, const Tensor& like, const char* what) {
-  need(lr, "lr");
-  TORCH_CHECK(lr.numel() == 1, what, ": lr must be a 1-element float32 GPU tensor");
-  TORCH_CHECK(lr.device() == like.device(), what, ": lr must be on the arenas' device");
-  return fp(lr);
-}
-
-// planes of sgd_flat / sgd_segmented: pointer to plane 0 (null: none), plane stride and count
-unsigned short* opt_planes(const OptT& planes, const Tensor& p, const char* what, long* ps, int* np) {
-  *ps = 0;
-  *np = 0;
-  if (!(planes.has_value() && planes->defined())) return nullptr;
-  const Tensor& t = *planes;
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 2 && t.size(1) == p.numel() &&
-                  ((t.scalar_type() == at::kBFloat16 && (t.size(0) == 1 || t.size(0) == 3)) ||
-                   (t.scalar_type() == at::kHalf && t.size(0) == 2)),
-              what, ": planes must be contiguous bfloat16 [1 or 3, p.numel()] or float16 [2, p.numel()]");
-  *np = (int)t.size(0);
-  *ps = t.stride(0);
-  return reinterpret_cast<unsigned short*>(t.data_ptr());
-}
-
 // table: float32 [T >= 1] the host built (schedule.lr_table); step: int64 [1]; lr: float32 [1].
 //   pos = from_device ? step[0] : host_pos ; lr[0] = table[min(pos, T - 1)] ; step[0] = pos + 1
 void lr_advance(Tensor table, Tensor step, Tensor lr, int64_t host_pos, bool from_device) {
@@ -341,46 +323,6 @@ void lr_advance(Tensor table, Tensor step, Tensor lr, int64_t host_pos, bool fro
   chk(dpa_lr_advance(fp(table), (long)table.numel(), reinterpret_cast<long*>(step.data_ptr<int64_t>()),
                      const_cast<float*>(l), (long)host_pos, from_device ? 1 : 0, cur_stream()),
       "lr_advance");
-}
-
-// sgd_flat with the rate read from lr[0] on the device
-void sgd_flat_dlr(Tensor p, Tensor g, Tensor buf, Tensor lr, double momentum, double wd, double gscale, bool first,
-                  int64_t offset, int64_t count, OptT planes) {
-  need(p, "p");
-  need(g, "g");
-  need(buf, "buf");
-  const float* l = lr_word(lr, p, "sgd_flat_dlr");
-  TORCH_CHECK(offset >= 0, "sgd_flat_dlr: offset must be >= 0");
-  if (count < 0) count = p.numel() - offset;
-  TORCH_CHECK(offset % 4 == 0 && count % 4 == 0, "sgd_flat_dlr: offset/count must be multiples of 4");
-  TORCH_CHECK(count >= 0 && offset + count <= p.numel() && p.numel() == g.numel() && p.numel() == buf.numel(),
-              "sgd_flat_dlr sizes");
-  long ps;
-  int np;
-  unsigned short* pl = opt_planes(planes, p, "sgd_flat_dlr", &ps, &np);
-  if (pl) pl += offset;
-  chk(dpa_sgd_flat_dlr(fp(p) + offset, fp(g) + offset, fp(buf) + offset, count, l, (float)momentum, (float)wd,
-                       (float)gscale, first ? 1 : 0, pl, ps, np, cur_stream()),
-      "sgd_flat_dlr");
-}
-
-// sgd_segmented with the rate read from lr[0] on the device
-void sgd_segmented_dlr(Tensor p, Tensor g, Tensor buf, Tensor bmap, Tensor table, Tensor lr, double momentum,
-                       double wd, bool first, OptT planes) {
-  opt_arenas(p, g, "sgd_segmented_dlr");
-  need(buf, "buf");
-  TORCH_CHECK(buf.numel() == p.numel(), "sgd_segmented_dlr sizes");
-  const long* bm = opt_table(bmap, "bmap");
-  need(table, "table");
-  const float* l = lr_word(lr, p, "sgd_segmented_dlr");
-  const int64_t nseg = table.numel() - 1;
-  TORCH_CHECK(nseg >= 1 && nseg <= dpa_opt_max_segments(), "sgd_segmented_dlr: table must be float32 [nseg + 1]");
-  long ps;
-  int np;
-  unsigned short* pl = opt_planes(planes, p, "sgd_segmented_dlr", &ps, &np);
-  chk(dpa_sgd_segmented_dlr(fp(p), fp(g), fp(buf), bm, bmap.size(0), p.numel(), (int)nseg, fp(table), l,
-                            (float)momentum, (float)wd, first ? 1 : 0, pl, ps, np, cur_stream()),
-      "sgd_segmented_dlr");
 }
 
 // Diagnostics: occupy the current stream for ~usec microseconds (one wave, bounded loop) and then
@@ -1449,12 +1391,6 @@ PYBIND11_MODULE(_C, m) {
   m.attr("OPT_CHUNK") = (int64_t)dpa_opt_chunk();  // chunk length of the block map (kernels/lars.hip)
   m.def("lr_advance", &lr_advance, py::arg("table"), py::arg("step"), py::arg("lr"), py::arg("host_pos"),
         py::arg("from_device"));
-  m.def("sgd_flat_dlr", &sgd_flat_dlr, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("lr"),
-        py::arg("momentum"), py::arg("wd"), py::arg("gscale"), py::arg("first"), py::arg("offset") = 0,
-        py::arg("count") = -1, py::arg("planes") = py::none());
-  m.def("sgd_segmented_dlr", &sgd_segmented_dlr, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("bmap"),
-        py::arg("table"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("first"),
-        py::arg("planes") = py::none());
   m.def("spin", &spin, py::arg("usec"), py::arg("done"));
   m.def("mean_of_w", &mean_of_w);
   m.def("add_inplace", &add_inplace);

@@ -24,6 +24,7 @@
 // never on the grid, and (b) adds a segment's chunks lane-strided in ascending order and then by
 // a fixed xor-shuffle tree, so the step is bitwise reproducible.
 #include "common.h"
+#include "optim_api.h"
 #include "sgd_update.h"
 
 constexpr int OPT_CHUNK = 8192;
@@ -136,36 +137,17 @@ __global__ __launch_bounds__(1024) void lars_finalize_kernel(const double* __res
   }
 }
 
-// (c) the update of sgd_flat_kernel<NP> (sgd_update.h) per chunk, with the chunk's segment ratio
-template <int NP>
+// (c) the update of sgd_flat_kernel<NP, LR> (sgd_update.h) per chunk, with the chunk's segment ratio
+template <int NP, class LR>
 __global__ __launch_bounds__(256) void sgd_segmented_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                             float* __restrict__ buf, const long* __restrict__ bmap,
                                                             long n, int nseg, const float* __restrict__ table,
-                                                            float lr, float momentum, float wd, int first,
+                                                            LR lrs, float momentum, float wd, int first,
                                                             u16* __restrict__ planes, long ps) {
   const long b = blockIdx.x;
   const long seg = bmap[3 * b], start = bmap[3 * b + 1], len = bmap[3 * b + 2];
   if (!chunk_ok(seg, start, len, n, nseg)) return;
-  const float r = table[seg], gmul = table[nseg];
-  const long i0 = start >> 2, i1 = (start + len) >> 2;
-  for (long i = i0 + threadIdx.x; i < i1; i += 256)
-    sgd_update4<NP>(p, g, buf, i, lr, momentum, wd, gmul, r, first, planes, ps);
-}
-
-// (c) with the learning rate read from device memory (lr_sched.hip), once per thread: a sibling
-// kernel, so sgd_segmented_kernel stays the code it is
-template <int NP>
-__global__ __launch_bounds__(256) void sgd_segmented_dlr_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                float* __restrict__ buf,
-                                                                const long* __restrict__ bmap, long n, int nseg,
-                                                                const float* __restrict__ table,
-                                                                const float* __restrict__ lrp, float momentum,
-                                                                float wd, int first, u16* __restrict__ planes,
-                                                                long ps) {
-  const long b = blockIdx.x;
-  const long seg = bmap[3 * b], start = bmap[3 * b + 1], len = bmap[3 * b + 2];
-  if (!chunk_ok(seg, start, len, n, nseg)) return;
-  const float lr = lrp[0];
+  const float lr = lrs.get();
   const float r = table[seg], gmul = table[nseg];
   const long i0 = start >> 2, i1 = (start + len) >> 2;
   for (long i = i0 + threadIdx.x; i < i1; i += 256)
@@ -190,42 +172,17 @@ extern "C" int dpa_lars_finalize(const double* partials, long nblocks, const lon
   return (int)hipGetLastError();
 }
 
-// planes: NP operand planes of the whole arena (plane stride ps), or nullptr / np = 0 (sgd.hip)
 extern "C" int dpa_sgd_segmented(float* p, const float* g, float* buf, const long* bmap, long nblocks, long n,
-                                 int nseg, const float* table, float lr, float momentum, float wd, int first,
-                                 u16* planes, long ps, int np, hipStream_t s) {
+                                 int nseg, const float* table, float lr, const float* lr_dev, float momentum,
+                                 float wd, int first, u16* planes, long ps, int np, hipStream_t s) {
   if (nblocks <= 0) return 0;
   const unsigned grid = (unsigned)nblocks;
-  if (planes && np == 3)
-    sgd_segmented_kernel<3><<<grid, 256, 0, s>>>(p, g, buf, bmap, n, nseg, table, lr, momentum, wd, first, planes, ps);
-  else if (planes && np == 2)
-    sgd_segmented_kernel<2><<<grid, 256, 0, s>>>(p, g, buf, bmap, n, nseg, table, lr, momentum, wd, first, planes, ps);
-  else if (planes && np == 1)
-    sgd_segmented_kernel<1><<<grid, 256, 0, s>>>(p, g, buf, bmap, n, nseg, table, lr, momentum, wd, first, planes, ps);
-  else
-    sgd_segmented_kernel<0><<<grid, 256, 0, s>>>(p, g, buf, bmap, n, nseg, table, lr, momentum, wd, first, nullptr, 0);
-  return (int)hipGetLastError();
-}
-
-// dpa_sgd_segmented with the rate in device memory (lr: one float32)
-extern "C" int dpa_sgd_segmented_dlr(float* p, const float* g, float* buf, const long* bmap, long nblocks, long n,
-                                     int nseg, const float* table, const float* lr, float momentum, float wd,
-                                     int first, u16* planes, long ps, int np, hipStream_t s) {
-  if (!lr) return -1;
-  if (nblocks <= 0) return 0;
-  const unsigned grid = (unsigned)nblocks;
-  if (planes && np == 3)
-    sgd_segmented_dlr_kernel<3><<<grid, 256, 0, s>>>(p, g, buf, bmap, n, nseg, table, lr, momentum, wd, first, planes,
-                                                     ps);
-  else if (planes && np == 2)
-    sgd_segmented_dlr_kernel<2><<<grid, 256, 0, s>>>(p, g, buf, bmap, n, nseg, table, lr, momentum, wd, first, planes,
-                                                     ps);
-  else if (planes && np == 1)
-    sgd_segmented_dlr_kernel<1><<<grid, 256, 0, s>>>(p, g, buf, bmap, n, nseg, table, lr, momentum, wd, first, planes,
-                                                     ps);
-  else
-    sgd_segmented_dlr_kernel<0><<<grid, 256, 0, s>>>(p, g, buf, bmap, n, nseg, table, lr, momentum, wd, first, nullptr,
-                                                     0);
+  with_rate(lr, lr_dev, [&](auto lrs) {
+    with_planes(planes, np, [&](auto NP) {
+      sgd_segmented_kernel<decltype(NP)::value, decltype(lrs)>
+          <<<grid, 256, 0, s>>>(p, g, buf, bmap, n, nseg, table, lrs, momentum, wd, first, planes, ps);
+    });
+  });
   return (int)hipGetLastError();
 }
 

@@ -4,11 +4,12 @@
 //   lr_advance   one wave, one lane:  pos = from_device ? *step : host_pos
 //                                     *lr = table[clamp(pos, 0, T - 1)] ; *step = pos + 1
 //
-// The update kernels' device-rate instances (sgd_flat_dlr_kernel in sgd.hip, sgd_segmented_dlr_kernel
-// in lars.hip) read *lr once per thread.  Eager steps pass the host's step count (host_pos), so the
-// host count stays the single truth; a captured step is launched with from_device = 1 and advances
-// by itself from replay to replay.
+// The update kernels' device-rate instances (sgd_flat_kernel in sgd.hip and sgd_segmented_kernel in
+// lars.hip with the rate source LrWord, sgd_update.h) read *lr once per thread.  Eager steps pass
+// the host's step count (host_pos), so the host count stays the single truth; a captured step is
+// launched with from_device = 1 and advances by itself from replay to replay.
 #include "common.h"
+#include "optim_api.h"
 
 __global__ __launch_bounds__(64) void lr_advance_kernel(const float* __restrict__ table, long T,
                                                         long* __restrict__ step, float* __restrict__ lr,

@@ -7,32 +7,18 @@
 //   d = g*scale + wd*p ; buf = first ? d : momentum*buf + d ; p -= lr*buf
 // (the per-element code is sgd_update.h, shared with the LARS / clipping update of lars.hip)
 #include "common.h"
+#include "optim_api.h"
 #include "sgd_update.h"
 
 // NP > 0: the updated parameters are also written as NP bf16 operand planes (plane stride ps, same
 // element index as the arena): the conv kernels' weight operands are refreshed in the same pass
-// instead of a separate split kernel per layer.
-template <int NP>
+// instead of a separate split kernel per layer.  LR: the rate source (sgd_update.h).
+template <int NP, class LR>
 __global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ buf, long n4, float lr, float momentum,
+                                                       float* __restrict__ buf, long n4, LR lrs, float momentum,
                                                        float wd, float gscale, int first, u16* __restrict__ planes,
                                                        long ps) {
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    sgd_update4<NP>(p, g, buf, i, lr, momentum, wd, gscale, 1.f, first, planes, ps);
-  }
-}
-
-// The same update with the learning rate read from device memory (lr_sched.hip: the rate of a
-// schedule, written by lr_advance earlier on the step's main stream), once per thread before the
-// loop.  A sibling kernel, so sgd_flat_kernel stays the code it is; the per-element code is shared.
-template <int NP>
-__global__ __launch_bounds__(256) void sgd_flat_dlr_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                           float* __restrict__ buf, long n4,
-                                                           const float* __restrict__ lrp, float momentum, float wd,
-                                                           float gscale, int first, u16* __restrict__ planes,
-                                                           long ps) {
-  const float lr = lrp[0];
+  const float lr = lrs.get();
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     sgd_update4<NP>(p, g, buf, i, lr, momentum, wd, gscale, 1.f, first, planes, ps);
@@ -58,38 +44,18 @@ static int grid_for(long n, int block) {
   return (int)g;
 }
 
-// planes: NP operand planes of the same arena slice (plane stride ps; np 2: fp16 pairs of p * H2_SW),
-// or nullptr / np = 0
-extern "C" int dpa_sgd_flat(float* p, const float* g, float* buf, long n, float lr, float momentum, float wd,
-                            float gscale, int first, u16* planes, long ps, int np, hipStream_t s) {
+extern "C" int dpa_sgd_flat(float* p, const float* g, float* buf, long n, float lr, const float* lr_dev,
+                            float momentum, float wd, float gscale, int first, u16* planes, long ps, int np,
+                            hipStream_t s) {
   if (n % 4) return -1;
   const long n4 = n / 4;
   const int grid = grid_for(n4, 256);
-  if (planes && np == 3)
-    sgd_flat_kernel<3><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, planes, ps);
-  else if (planes && np == 2)
-    sgd_flat_kernel<2><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, planes, ps);
-  else if (planes && np == 1)
-    sgd_flat_kernel<1><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, planes, ps);
-  else
-    sgd_flat_kernel<0><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, nullptr, 0);
-  return (int)hipGetLastError();
-}
-
-// dpa_sgd_flat with the rate in device memory (lr: one float32)
-extern "C" int dpa_sgd_flat_dlr(float* p, const float* g, float* buf, long n, const float* lr, float momentum,
-                                float wd, float gscale, int first, u16* planes, long ps, int np, hipStream_t s) {
-  if (n % 4 || !lr) return -1;
-  const long n4 = n / 4;
-  const int grid = grid_for(n4, 256);
-  if (planes && np == 3)
-    sgd_flat_dlr_kernel<3><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, planes, ps);
-  else if (planes && np == 2)
-    sgd_flat_dlr_kernel<2><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, planes, ps);
-  else if (planes && np == 1)
-    sgd_flat_dlr_kernel<1><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, planes, ps);
-  else
-    sgd_flat_dlr_kernel<0><<<grid, 256, 0, s>>>(p, g, buf, n4, lr, momentum, wd, gscale, first, nullptr, 0);
+  with_rate(lr, lr_dev, [&](auto lrs) {
+    with_planes(planes, np, [&](auto NP) {
+      sgd_flat_kernel<decltype(NP)::value, decltype(lrs)>
+          <<<grid, 256, 0, s>>>(p, g, buf, n4, lrs, momentum, wd, gscale, first, planes, ps);
+    });
+  });
   return (int)hipGetLastError();
 }
 

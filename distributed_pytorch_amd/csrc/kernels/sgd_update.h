@@ -8,7 +8,44 @@
 // contraction, so that with r = 1 (x * 1 is exact) every remaining operation is the flat kernel's
 // and both kernels give the same bits.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
+
+// The learning rate of an update kernel, read once per thread before its loop: a kernel argument
+// (the constant rate), or one float32 word in device memory (lr_sched.hip: the rate of a schedule,
+// written by lr_advance earlier on the step's main stream).
+struct LrValue {
+  float v;
+  __device__ __forceinline__ float get() const { return v; }
+};
+struct LrWord {
+  const float* p;
+  __device__ __forceinline__ float get() const { return p[0]; }
+};
+
+// f(rate source) for a launcher's (lr, lr_dev) pair: a non-null lr_dev selects the device word
+template <class F>
+inline void with_rate(float lr, const float* lr_dev, F&& f) {
+  if (lr_dev)
+    f(LrWord{lr_dev});
+  else
+    f(LrValue{lr});
+}
+
+// f(std::integral_constant<int, NP>) for a launcher's (planes, np) pair: NP in {0, 1, 2, 3}, 0
+// without planes
+template <class F>
+inline void with_planes(const u16* planes, int np, F&& f) {
+  if (planes && np == 3)
+    f(std::integral_constant<int, 3>{});
+  else if (planes && np == 2)
+    f(std::integral_constant<int, 2>{});
+  else if (planes && np == 1)
+    f(std::integral_constant<int, 1>{});
+  else
+    f(std::integral_constant<int, 0>{});
+}
 
 __device__ __forceinline__ float mul_unfused(float a, float b) {
 #pragma clang fp contract(off)

@@ -13,10 +13,11 @@ step is a static schedule of native kernels over persistent buffers:
             with flipped taps; its split-K slabs are summed inside the next bn_bwd)
   split-K   forward/dgrad partial slabs are never reduced by a separate pass: bn_fwd_stats /
             bn_bwd sum them while computing their statistics
-  update    sgd_flat over the flat parameter/grad/momentum arenas (one launch); with LARS or
-            gradient clipping: sqnorm_partials → lars_finalize → sgd_segmented (three launches)
+  update    (optim.FlatUpdate) sgd_flat over the flat parameter/grad/momentum arenas (one launch);
+            with LARS or gradient clipping: sqnorm_partials → lars_finalize → sgd_segmented (three
+            launches)
   schedule  (set_lr_schedule only) lr_advance first: the step's rate from the host-built table
-            into a device word, which the update kernels' _dlr instances read
+            into a device word, which the update kernels then read as their rate
 
 Parameters/grads/momentum are three :class:`~distributed_pytorch_amd.utils.arena.Arena` s with
 identical layout (reference ``named_parameters()`` order; conv weights stored KRSC, the first
@@ -38,7 +39,8 @@ import torch
 from . import _ext
 from .models.vgg import VGGSpec
 from .ops import cpu_ref
-from .utils.arena import Arena, block_map
+from .optim import FlatUpdate, ScheduleTensors
+from .utils.arena import Arena
 from .utils.streams import DevEvent, StreamJoin
 
 
@@ -145,7 +147,7 @@ def pos_ok(kind: str, tile: int, h: int, w: int, cred: int, cout: int) -> bool:
     return worst <= nspx
 
 
-class VGGEngine:
+class VGGEngine(ScheduleTensors):
     """Static-schedule trainer.  ``impl`` selects the conv kernels of every layer whose input has a
     multiple of 8 channels (the 3-channel first layer always runs the fp32-MFMA kernel):
 
@@ -206,10 +208,9 @@ class VGGEngine:
         if not 0.0 <= self.label_smoothing < 1.0:
             raise ValueError(f"label_smoothing must be in [0, 1), got {self.label_smoothing}")
         self._mix = None  # (target2, lam) of the training batches: set_mix
-        # learning-rate schedule (set_lr_schedule): the host-built float32 table and its spec; on the
-        # GPU also the table's device copy and the words step_dev / lr_dev, which exist only while a
-        # schedule is set.  None: the constant rate self.lr, a kernel argument.
-        self._lr_table = None
+        # learning-rate schedule (set_lr_schedule): its spec; the table's device copy and the words
+        # step_dev / lr_dev exist only while one is set.  None: the constant rate self.lr, a kernel
+        # argument.
         self.lr_spec: Optional[dict] = None
         dev = self.device
         L = self.spec.convs
@@ -221,13 +222,8 @@ class VGGEngine:
         self.params = Arena(entries, dev)
         self.grads = self.params.like()
         self.mom = self.params.like()
-        if self.whole_arena_step:
-            self._opt_bmap, self._opt_segs = block_map(self.params.segments(), int(self.K.OPT_CHUNK),
-                                                       self.optimizer == "lars", dev)
-            nseg = self._opt_segs.shape[0]
-            self._opt_partials = torch.zeros(self._opt_bmap.shape[0], 2, dtype=torch.float64, device=dev)
-            self._opt_table = torch.ones(nseg + 1, dtype=torch.float32, device=dev)
-            self._opt_stats = torch.zeros(2 * nseg + 2, dtype=torch.float64, device=dev)
+        self.upd = FlatUpdate(self.K, self.params.flat, self.params.segments() if self.whole_arena_step else None,
+                              self.optimizer == "lars", self.trust_coef, self.clip_grad_norm, self.lars_eps)
         self.buffers = Arena([(f"{l.bn_key}.{b}", (l.cout,)) for l in L for b in ("running_mean", "running_var")],
                              dev)
         self.nbt = torch.zeros(len(L), dtype=torch.int64, device=dev)
@@ -761,51 +757,18 @@ class VGGEngine:
         (one wave), which writes the step's rate into ``lr_dev``, and the update kernels read it
         there -- so a captured step follows the schedule from replay to replay.  The position is
         ``steps_taken``: nothing else is saved or restored."""
-        if table is None:
-            self._lr_table = self.lr_spec = None
-            for a in ("table_dev", "step_dev", "lr_dev"):
-                if hasattr(self, a):
-                    delattr(self, a)
-            return
-        from .schedule import as_table, table_spec
-
-        tab = as_table(table)
-        self.lr_spec = table_spec(table, spec)
-        self._lr_table = tab
-        self._lr_last = float(tab[0])  # CPU backend: the rate and the counter as host values
-        self._lr_pos = 0
-        if self.K is not cpu_ref:
-            dev = self.params.flat.device
-            self.table_dev = torch.from_numpy(tab.copy()).to(dev)
-            self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-            self.lr_dev = self.table_dev[:1].clone()
-
-    def _lr_advance(self):
-        """First launch of a scheduled step on the main stream: lr_dev = table[min(step, T - 1)].
-        Eager: the step is the host's count (steps_taken stays the single truth, so whatever
-        restores it -- a checkpoint, the comm tuner -- moves the schedule with it).  Under capture:
-        the device counter, so that every replay advances by itself (GraphedStep seeds it)."""
-        tab = self._lr_table
-        if self.K is cpu_ref:
-            self._lr_last = float(tab[min(self.steps_taken, len(tab) - 1)])
-            self._lr_pos = self.steps_taken + 1
-            return
-        self.K.lr_advance(self.table_dev, self.step_dev, self.lr_dev, self.steps_taken,
-                          torch.cuda.is_current_stream_capturing())
+        self.upd.set_schedule(table, spec)
+        self.lr_spec = self.upd.spec
 
     def current_lr(self) -> float:
         """The learning rate of the most recent step (synchronises); ``self.lr`` without a schedule.
         Before the first step of a schedule: its first value."""
-        if self._lr_table is None:
-            return self.lr
-        return self._lr_last if self.K is cpu_ref else float(self.lr_dev.item())
+        return self.lr if self.lr_spec is None else self.upd.current_lr()
 
     def lr_position(self) -> int:
-        """The schedule's step counter (on the GPU the device word; synchronises): the number of
-        scheduled steps begun, counted from the global step 0."""
-        if self._lr_table is None:
-            raise ValueError("lr_position: no learning-rate schedule is set")
-        return self._lr_pos if self.K is cpu_ref else int(self.step_dev.item())
+        """The schedule's step counter (the device word; synchronises): the number of scheduled
+        steps begun, counted from the global step 0."""
+        return self.upd.lr_position()
 
     # ------------------------------------------------------------------ training step
     def forward_backward(self, x: torch.Tensor, target: torch.Tensor,
@@ -829,7 +792,7 @@ class VGGEngine:
         K, P, G = self.K, self.params, self.grads
         n = x.shape[0]
         L = self.spec.convs
-        if self._lr_table is not None:
+        if self.lr_spec is not None:
             # The step's rate, before anything else on the main stream.  Every update of this step
             # that reads lr_dev is ordered behind it: the whole-arena update runs on the main stream
             # after backward; a per-bucket update (DPA_FUSED_STEP=1) runs on the wgrad or comm
@@ -838,7 +801,7 @@ class VGGEngine:
             # shard updates run on the main stream after finish().  And it overwrites lr_dev only
             # after the previous step's readers: the main stream joined the wgrad and comm streams
             # (end of backward, sync.finish()) before that step's update returned.
-            self._lr_advance()
+            self.upd.advance(self.steps_taken)
         buffers_wait = pre_forward() if pre_forward is not None else None
         epoch = 0
         if self.ksignal and not torch.cuda.is_current_stream_capturing():
@@ -1072,48 +1035,17 @@ class VGGEngine:
 
     def sgd_step(self, grad_scale: float = 1.0, offset: int = 0, count: int = -1, first: Optional[bool] = None):
         """Fused SGD over the arena (or the [offset, offset+count) slice of it)."""
-        self._sgd(grad_scale, offset, count, self.steps_taken == 0 if first is None else first)
-
-    def _sgd(self, grad_scale: float, offset: int, count: int, first: bool):
-        # a schedule's rate: on the GPU the device word lr_dev (the _dlr entry points read it), on the
-        # CPU backend the table's value for this step, handed to the same functions as self.lr
-        dlr = self._lr_table is not None and self.K is not cpu_ref
-        lr = self.lr if self._lr_table is None else self._lr_last
-        if self.whole_arena_step:
-            n = self.params.flat.numel()
-            if offset != 0 or (count >= 0 and count != n):
-                raise ValueError("sgd_step: LARS / gradient clipping update the whole arena (the norms of a "
-                                 f"slice are not defined); got offset={offset}, count={count}")
-            K, p, g = self.K, self.params.flat, self.grads.flat
-            K.sqnorm_partials(p, g, self._opt_bmap, self._opt_partials, self._opt_segs.shape[0])
-            K.lars_finalize(self._opt_partials, self._opt_segs, self._opt_table, self._opt_stats, grad_scale,
-                            self.clip_grad_norm, self.trust_coef, self.weight_decay, self.lars_eps)
-            if dlr:
-                K.sgd_segmented_dlr(p, g, self.mom.flat, self._opt_bmap, self._opt_table, self.lr_dev, self.momentum,
-                                    self.weight_decay, first, self.wplanes)
-            else:
-                K.sgd_segmented(p, g, self.mom.flat, self._opt_bmap, self._opt_table, lr, self.momentum,
-                                self.weight_decay, first, self.wplanes)
-            return
-        if dlr:
-            self.K.sgd_flat_dlr(self.params.flat, self.grads.flat, self.mom.flat, self.lr_dev, self.momentum,
-                                self.weight_decay, grad_scale, first, offset, count, self.wplanes)
-            return
-        self.K.sgd_flat(self.params.flat, self.grads.flat, self.mom.flat, lr, self.momentum, self.weight_decay,
-                        grad_scale, first, offset, count, self.wplanes)
+        self.upd.update(self.params.flat, self.grads.flat, self.mom.flat, self.lr, self.momentum, self.weight_decay,
+                        grad_scale, self.steps_taken == 0 if first is None else first, offset, count, self.wplanes)
 
     def opt_stats(self) -> dict:
         """The last LARS / clipping step's norms as Python values (synchronises): ``grad_norm`` (of
         the scaled gradient, before clipping), ``clip_coef``, and per tensor name ``p_norm``,
         ``g_norm`` and ``trust_ratio`` under ``tensors``."""
-        if not self.whole_arena_step:
-            raise ValueError("opt_stats: the engine runs plain SGD (no LARS, no gradient clipping)")
-        st, tb = self._opt_stats.cpu().tolist(), self._opt_table.cpu().tolist()
-        names = self.params.names()
-        S = len(names)
-        return {"grad_norm": st[2 * S], "clip_coef": st[2 * S + 1],
-                "tensors": {n: {"p_norm": st[i], "g_norm": st[S + i], "trust_ratio": tb[i]}
-                            for i, n in enumerate(names)}}
+        st = self.upd.stats()
+        return {"grad_norm": st["grad_norm"], "clip_coef": st["clip_coef"],
+                "tensors": {n: {k: st[k][i] for k in ("p_norm", "g_norm", "trust_ratio")}
+                            for i, n in enumerate(self.params.names())}}
 
     def wait_signal(self, signal):
         """The current stream waits (one polling wave, bounded) for a ``(flag, value)`` signal."""

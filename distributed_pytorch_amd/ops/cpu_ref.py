@@ -25,7 +25,13 @@ def _nhwc(t):
 
 
 # ---------------------------------------------------------------- optimizer / elementwise
+def _rate(lr):
+    """The rate of the update functions: a float, or the value of a 1-element tensor."""
+    return float(lr[0]) if torch.is_tensor(lr) else lr
+
+
 def sgd_flat(p, g, buf, lr, momentum, wd, gscale, first, offset=0, count=-1, planes=None):
+    lr = _rate(lr)
     if count < 0:
         count = p.numel() - offset
     sl = slice(offset, offset + count)
@@ -81,6 +87,7 @@ def sgd_segmented(p, g, buf, bmap, table, lr, momentum, wd, first, planes=None):
     """sgd_flat over the chunks of bmap with the segment's trust ratio and the table's gradient
     multiplier:  d = (g * gmul + wd * p) * r_s ; buf = first ? d : momentum * buf + d ; p -= lr * buf
     (LARS with the learning rate outside the momentum, as apex LARC / torchlars)."""
+    lr = _rate(lr)
     S = table.numel() - 1
     gmul = table[S].to(p.dtype)
     r = torch.ones_like(p)
@@ -107,16 +114,6 @@ def lr_advance(table, step, lr, host_pos, from_device):
     pos = int(step[0]) if from_device else int(host_pos)
     lr[0] = table[min(max(pos, 0), table.numel() - 1)]
     step[0] = pos + 1
-
-
-def sgd_flat_dlr(p, g, buf, lr, momentum, wd, gscale, first, offset=0, count=-1, planes=None):
-    """sgd_flat with the rate read from the 1-element float32 tensor lr."""
-    sgd_flat(p, g, buf, float(lr[0]), momentum, wd, gscale, first, offset, count, planes)
-
-
-def sgd_segmented_dlr(p, g, buf, bmap, table, lr, momentum, wd, first, planes=None):
-    """sgd_segmented with the rate read from the 1-element float32 tensor lr."""
-    sgd_segmented(p, g, buf, bmap, table, float(lr[0]), momentum, wd, first, planes)
 
 
 def split_bf16(x, np_):

@@ -23,7 +23,10 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn as nn
 
+from .. import _ext
+from ..ops import cpu_ref
 from ..ops.functional import NPLANES
+from ..optim import FlatUpdate, ScheduleTensors
 from .comm import Comm, NullComm
 
 ALIGN = 64
@@ -252,110 +255,52 @@ class DistributedDataParallel(nn.Module):
         return len(self._buckets)
 
 
-class FlatSGD:
+class FlatSGD(ScheduleTensors):
     """torch.optim.SGD semantics (momentum, dampening 0, weight decay, no nesterov) as ONE fused
     kernel over the DDP arenas; ``step(grad_scale)`` folds the 1/W DDP scale in.
 
     ``trust_coef`` (not None): LARS, a trust ratio on every parameter of rank >= 2;
     ``clip_grad_norm`` > 0: global-norm gradient clipping.  Either makes the step the three
-    launches of kernels/lars.hip over the wrapper's parameters as segments (fp32 arena on the GPU;
-    anything else runs ops/cpu_ref).
+    launches of kernels/lars.hip over the wrapper's parameters as segments.
 
     ``schedule``: a learning-rate table (``schedule.lr_table``) indexed by ``self.steps``; ``lr`` is
-    then unused.  On the GPU ``step()`` starts with ``lr_advance`` (kernels/lr_sched.hip) and the
-    update reads the rate from device memory, so a captured ``step()`` follows the schedule; the
-    oracle path hands the table's value to the same reference functions."""
+    then unused.  ``step()`` starts with ``lr_advance`` (kernels/lr_sched.hip) and the update reads
+    the rate from device memory, so a captured ``step()`` follows the schedule.
+
+    The launches and their state are ``optim.FlatUpdate``'s, on the native kernels for an fp32 arena
+    on the GPU and on the same functions of ops/cpu_ref for a CPU arena."""
 
     def __init__(self, ddp: DistributedDataParallel, lr: float, momentum: float = 0.0, weight_decay: float = 0.0,
                  trust_coef: Optional[float] = None, clip_grad_norm: Optional[float] = None, lars_eps: float = 1e-9,
                  schedule=None):
         self.ddp = ddp
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
-        self.buf = torch.zeros_like(ddp.flat_params)
+        p = ddp.flat_params
+        self.buf = torch.zeros_like(p)
         self.steps = 0
-        self._lr_table = self.lr_spec = None
-        if schedule is not None:
-            from ..schedule import as_table, table_spec
-
-            p = ddp.flat_params
-            self._lr_table, self.lr_spec = as_table(schedule), table_spec(schedule)
-            if p.is_cuda and p.dtype == torch.float32:
-                self.table_dev = torch.from_numpy(self._lr_table.copy()).to(p.device)
-                self.step_dev = torch.zeros(1, dtype=torch.int64, device=p.device)
-                self.lr_dev = self.table_dev[:1].clone()
         self.trust_coef, self.lars_eps = trust_coef, lars_eps
         self.clip_grad_norm = float(clip_grad_norm or 0.0)
         self.segmented = trust_coef is not None or self.clip_grad_norm > 0
-        if self.segmented:
-            from ..utils.arena import block_map
-
-            p = ddp.flat_params
-            self._native = p.is_cuda and p.dtype == torch.float32
-            K = self._backend()
-            segs = [(o, (q.numel() + ALIGN - 1) // ALIGN * ALIGN, q.ndim)
-                    for o, q in zip(ddp._pflat.offsets, ddp._params)]
-            self._bmap, self._segs = block_map(segs, int(K.OPT_CHUNK), trust_coef is not None, p.device)
-            nseg = self._segs.shape[0]
-            self._partials = torch.zeros(self._bmap.shape[0], 2, dtype=torch.float64, device=p.device)
-            # (the oracle path keeps the ratios in the arena's own precision)
-            self._table = torch.ones(nseg + 1, dtype=torch.float32 if self._native else p.dtype, device=p.device)
-            self._stats = torch.zeros(2 * nseg + 2, dtype=torch.float64, device=p.device)
-
-    def _backend(self):
-        if self._native:
-            from .. import _ext
-
-            return _ext.require()
-        from ..ops import cpu_ref
-
-        return cpu_ref
+        segs = [(o, (q.numel() + ALIGN - 1) // ALIGN * ALIGN, q.ndim) for o, q in zip(ddp._pflat.offsets, ddp._params)]
+        # the oracle serves CPU arenas, and LARS / clipping on a GPU arena of another precision; plain
+        # SGD on such an arena has no kernel and no stand-in (sgd_flat refuses its dtype)
+        K = _ext.require() if p.is_cuda and (p.dtype == torch.float32 or not self.segmented) else cpu_ref
+        self.upd = FlatUpdate(K, p, segs if self.segmented else None, trust_coef is not None, trust_coef or 0.0,
+                              self.clip_grad_norm, lars_eps)
+        self.upd.set_schedule(schedule)
+        self.lr_spec = self.upd.spec
 
     def zero_grad(self, set_to_none: bool = False):
         self.ddp.zero_grad()
 
     @torch.no_grad()
     def step(self, grad_scale: float = 1.0):
-        p, g = self.ddp.flat_params, self.ddp.flat_grads
-        lr, dlr = self.lr, False
-        if self._lr_table is not None:
-            dlr = hasattr(self, "lr_dev")
-            if dlr:  # first launch of the step: the rate that the update kernel below reads
-                from .. import _ext
-
-                _ext.require().lr_advance(self.table_dev, self.step_dev, self.lr_dev, self.steps,
-                                          torch.cuda.is_current_stream_capturing())
-            else:
-                lr = float(self._lr_table[min(self.steps, len(self._lr_table) - 1)])
-        if self.segmented:
-            K = self._backend()
-            K.sqnorm_partials(p, g, self._bmap, self._partials, self._segs.shape[0])
-            K.lars_finalize(self._partials, self._segs, self._table, self._stats, grad_scale, self.clip_grad_norm,
-                            self.trust_coef or 0.0, self.weight_decay, self.lars_eps)
-            if dlr and self._native:
-                K.sgd_segmented_dlr(p, g, self.buf, self._bmap, self._table, self.lr_dev, self.momentum,
-                                    self.weight_decay, self.steps == 0, self.ddp.weight_planes)
-            else:
-                K.sgd_segmented(p, g, self.buf, self._bmap, self._table, lr, self.momentum, self.weight_decay,
-                                self.steps == 0, self.ddp.weight_planes if self._native else None)
-        elif p.is_cuda:
-            from .. import _ext
-
-            if dlr:
-                _ext.require().sgd_flat_dlr(p, g, self.buf, self.lr_dev, self.momentum, self.weight_decay, grad_scale,
-                                            self.steps == 0, 0, -1, self.ddp.weight_planes)
-            else:
-                _ext.require().sgd_flat(p, g, self.buf, lr, self.momentum, self.weight_decay, grad_scale,
-                                        self.steps == 0, 0, -1, self.ddp.weight_planes)
-        else:
-            from ..ops import cpu_ref
-
-            cpu_ref.sgd_flat(p, g, self.buf, lr, self.momentum, self.weight_decay, grad_scale, self.steps == 0)
+        if self.lr_spec is not None:  # first launch of the step: the rate that the update below reads
+            self.upd.advance(self.steps)
+        self.upd.update(self.ddp.flat_params, self.ddp.flat_grads, self.buf, self.lr, self.momentum,
+                        self.weight_decay, grad_scale, self.steps == 0, planes=self.ddp.weight_planes)
         self.steps += 1
 
     def current_lr(self) -> float:
         """The rate of the most recent step (synchronises); ``self.lr`` without a schedule."""
-        if self._lr_table is None:
-            return self.lr
-        if hasattr(self, "lr_dev"):
-            return float(self.lr_dev.item())
-        return float(self._lr_table[min(max(self.steps - 1, 0), len(self._lr_table) - 1)])
+        return self.lr if self.lr_spec is None else self.upd.current_lr()

@@ -1,7 +1,7 @@
 """Learning-rate schedules on the GPU (kernels/lr_sched.hip and the device-rate instances of the
 update kernels in sgd.hip / lars.hip).  Every new path is pinned bitwise against a path the project
-already has: lr_advance against the host's table, sgd_flat_dlr / sgd_segmented_dlr against
-sgd_flat / sgd_segmented given the same float32 rate as an argument, and the scheduled engine
+already has: lr_advance against the host's table, sgd_flat / sgd_segmented given the rate as a
+device word against the same calls given the same float32 rate as a float, and the scheduled engine
 (eager, captured, resumed into a capture, per-bucket update placement) against an engine whose
 constant rate is set to float(table[t]) by hand before every step."""
 import pytest
@@ -74,14 +74,29 @@ def test_bindings_check_arguments():
         C_.lr_advance(td, step, lr, -1, False)
     p = torch.zeros(64, device="cuda")
     with pytest.raises(RuntimeError):
-        C_.sgd_flat_dlr(p, p.clone(), p.clone(), lr.cpu(), 0.9, 1e-4, 1.0, False)  # CPU rate
+        C_.sgd_flat(p, p.clone(), p.clone(), lr.cpu(), 0.9, 1e-4, 1.0, False)  # CPU rate
     with pytest.raises(RuntimeError):
-        C_.sgd_flat_dlr(p, p.clone(), p.clone(), lr.double(), 0.9, 1e-4, 1.0, False)
-    with pytest.raises(RuntimeError):
-        C_.sgd_flat_dlr(p, p.clone(), p.clone(), lr, 0.9, 1e-4, 1.0, False, 32, 64)  # slice past the end
-    with pytest.raises(RuntimeError):
-        C_.sgd_flat_dlr(p, p.clone(), p.clone(), lr, 0.9, 1e-4, 1.0, False, 2, 4)  # unaligned slice
+        C_.sgd_flat(p, p.clone(), p.clone(), lr.double(), 0.9, 1e-4, 1.0, False)
+    for rate in (lr, 0.1):
+        with pytest.raises(RuntimeError):
+            C_.sgd_flat(p, p.clone(), p.clone(), rate, 0.9, 1e-4, 1.0, False, 32, 64)  # slice past the end
+        with pytest.raises(RuntimeError):
+            C_.sgd_flat(p, p.clone(), p.clone(), rate, 0.9, 1e-4, 1.0, False, 2, 4)  # unaligned slice
     torch.cuda.synchronize()
+
+
+def test_sgd_flat_rejects_negative_offset():
+    """offset = -4, count = 8 satisfies the alignment and upper-bound checks; it is refused before
+    any launch, with a float rate and with a device rate.  p, g, buf are the views base[64:128], so
+    that a build without the check would write inside a live allocation."""
+    C_ = _C()
+    lr = torch.full((1,), 0.1, device="cuda")
+    bases = [torch.ones(128, device="cuda") for _ in range(3)]
+    p, g, buf = (b[64:128] for b in bases)
+    for rate in (0.1, lr):
+        with pytest.raises(RuntimeError, match="offset"):
+            C_.sgd_flat(p, g, buf, rate, 0.9, 1e-4, 1.0, False, -4, 8)
+    assert all(bool((b == 1).all()) for b in bases)
 
 
 # ------------------------------------------------------------------ update kernels
@@ -112,7 +127,7 @@ def test_sgd_flat_dlr_same_bits_as_sgd_flat(n, offset, count, np_, first):
     lr = torch.tensor([RATE], device="cuda")
     assert lr.item() == RATE
     C_.sgd_flat(pa, g, ba, RATE, 0.9, 1e-4, 0.5, first, offset, count, pla)
-    C_.sgd_flat_dlr(pb, g, bb, lr, 0.9, 1e-4, 0.5, first, offset, count, plb)
+    C_.sgd_flat(pb, g, bb, lr, 0.9, 1e-4, 0.5, first, offset, count, plb)
     torch.cuda.synchronize()
     assert torch.equal(pa, pb) and torch.equal(ba, bb)
     hi = n if count < 0 else offset + count
@@ -131,7 +146,7 @@ def test_sgd_flat_dlr_same_bits_as_sgd_flat(n, offset, count, np_, first):
 @pytest.mark.parametrize("np_", [0, 1, 3, 2])
 def test_sgd_segmented_dlr_same_bits_as_sgd_segmented(np_, first):
     """Two segments of 64 + 8256 elements (the second spans two chunks) with a non-trivial ratio
-    table: the device-rate kernel gives the bits of sgd_segmented."""
+    table: the device-rate instance gives the bits of the float-rate one."""
     from distributed_pytorch_amd.utils.arena import block_map
 
     C_ = _C()
@@ -144,7 +159,7 @@ def test_sgd_segmented_dlr_same_bits_as_sgd_segmented(np_, first):
     pla, plb = _planes(np_, n), _planes(np_, n)
     lr = torch.tensor([RATE], device="cuda")
     C_.sgd_segmented(pa, g, ba, bmap, table, RATE, 0.9, 1e-4, first, pla)
-    C_.sgd_segmented_dlr(pb, g, bb, bmap, table, lr, 0.9, 1e-4, first, plb)
+    C_.sgd_segmented(pb, g, bb, bmap, table, lr, 0.9, 1e-4, first, plb)
     torch.cuda.synchronize()
     assert torch.equal(pa, pb) and torch.equal(ba, bb)
     assert not torch.equal(pb[:64], p[:64]) and not torch.equal(pb[8192 + 64:], p[8192 + 64:])
