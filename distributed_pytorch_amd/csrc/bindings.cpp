@@ -242,6 +242,29 @@ void sgd_flat(Tensor p, Tensor g, Tensor buf, Rate lr, double momentum, double w
       "sgd_flat");
 }
 
+// ---- gradient accumulation (kernels/grad_fold.hip) ----
+// mode 0 store: acc = g   1 add: acc = acc + g   2 merge: g = acc + g, over [offset, offset + count)
+// of two flat fp32 arenas of one length.  Every refused argument is a ValueError before any launch.
+void grad_fold(Tensor acc, Tensor g, int64_t mode, int64_t offset, int64_t count) {
+  auto bad = [](const std::string& msg) { throw py::value_error("grad_fold: " + msg); };
+  for (const Tensor* t : {&acc, &g}) {
+    if (!t->is_cuda()) bad("acc and g must be GPU tensors");
+    if (t->scalar_type() != at::kFloat) bad("acc and g must be float32");
+    if (!t->is_contiguous()) bad("acc and g must be contiguous");
+  }
+  if (acc.device() != g.device()) bad("acc and g must be on one device");
+  if (acc.numel() != g.numel()) bad("acc and g must have one length");
+  if (mode < 0 || mode > 2) bad("mode must be 0 (store), 1 (add) or 2 (merge)");
+  if (offset < 0) bad("offset must be >= 0");
+  if (count < -1) bad("count must be >= 0 (or -1: to the end)");
+  if (offset > acc.numel()) bad("the slice ends past the arena");
+  if (count < 0) count = acc.numel() - offset;
+  if (offset % 4 != 0 || count % 4 != 0) bad("offset and count must be multiples of 4");
+  if (count > acc.numel() - offset) bad("the slice ends past the arena");
+  if (count == 0) return;
+  chk(dpa_grad_fold(fp(acc) + offset, fp(g) + offset, count, (int)mode, cur_stream()), "grad_fold");
+}
+
 // ---- LARS / global-norm clipping over the arenas (kernels/lars.hip) ----
 // bmap: int64 [nblocks, 3] (segment, start, length) per chunk; segs: int64 [nseg, 3] (first chunk,
 // chunks, adapted) per segment.  Both are device tables the host built once (utils/arena.block_map),
@@ -1388,7 +1411,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("sgd_segmented", &sgd_segmented, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("bmap"),
         py::arg("table"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("first"),
         py::arg("planes") = py::none());
-  m.attr("OPT_CHUNK") = (int64_t)dpa_opt_chunk();  // chunk length of the block map (kernels/lars.hip)
+  m.def("grad_fold", &grad_fold, py::arg("acc"), py::arg("g"), py::arg("mode"), py::arg("offset") = 0,
+        py::arg("count") = -1);
+  m.attr("OPT_CHUNK") =(int64_t)dpa_opt_chunk();  // chunk length of the block map (kernels/lars.hip)
   m.def("lr_advance", &lr_advance, py::arg("table"), py::arg("step"), py::arg("lr"), py::arg("host_pos"),
         py::arg("from_device"));
   m.def("spin", &spin, py::arg("usec"), py::arg("done"));

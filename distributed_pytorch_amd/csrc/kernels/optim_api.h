@@ -1,4 +1,4 @@
-// The optimizer's entry points (sgd.hip, lars.hip, lr_sched.hip), declared once: the kernel files
+// The optimizer's entry points (sgd.hip, lars.hip, lr_sched.hip, grad_fold.hip), declared once: the kernel files
 // that define them and the bindings that call them include this header, so the compiler checks
 // every definition against its use.
 #pragma once
@@ -17,6 +17,9 @@ int dpa_sqnorm_partials(const float* p, const float* g, const long* bmap, long n
 int dpa_lars_finalize(const double* partials, long nblocks, const long* segs, int nseg, float* table, double* stats,
                       double gs, double max_norm, double trust, double wd, double eps, hipStream_t s);
 int dpa_lr_advance(const float* table, long T, long* step, float* lr, long host_pos, int from_device, hipStream_t s);
+// gradient accumulation (grad_fold.hip) over n elements (n % 4 == 0, else -1):
+// mode 0 store: acc = g   1 add: acc = acc + g   2 merge: g = acc + g
+int dpa_grad_fold(float* acc, float* g, long n, int mode, hipStream_t s);
 int dpa_opt_chunk();
 int dpa_opt_max_segments();
 }

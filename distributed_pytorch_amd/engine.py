@@ -222,7 +222,10 @@ class VGGEngine(ScheduleTensors):
         self.params = Arena(entries, dev)
         self.grads = self.params.like()
         self.mom = self.params.like()
-        self.upd = FlatUpdate(self.K, self.params.flat, self.params.segments() if self.whole_arena_step else None,
+        # gradient accumulation (accum.AccumulatedStep): the fp32 arena the micro-steps' gradients are
+        # folded into, laid out like grads; allocated by the first fold, None until then
+        self.gacc: Optional[Arena] = None
+        self.upd =FlatUpdate(self.K, self.params.flat, self.params.segments() if self.whole_arena_step else None,
                               self.optimizer == "lars", self.trust_coef, self.clip_grad_norm, self.lars_eps)
         self.buffers = Arena([(f"{l.bn_key}.{b}", (l.cout,)) for l in L for b in ("running_mean", "running_var")],
                              dev)
@@ -1038,6 +1041,14 @@ class VGGEngine(ScheduleTensors):
         self.upd.update(self.params.flat, self.grads.flat, self.mom.flat, self.lr, self.momentum, self.weight_decay,
                         grad_scale, self.steps_taken == 0 if first is None else first, offset, count, self.wplanes)
 
+    def grad_fold(self, mode: int, offset: int = 0, count: int = -1):
+        """Gradient accumulation over the arenas (or the [offset, offset+count) slice), on the current
+        stream (kernels/grad_fold.hip): mode 0 ``gacc = grads``, 1 ``gacc += grads``, 2 ``grads =
+        gacc + grads``.  The accumulator arena is allocated here the first time."""
+        if self.gacc is None:
+            self.gacc = self.grads.like()
+        self.K.grad_fold(self.gacc.flat, self.grads.flat, mode, offset, count)
+
     def opt_stats(self) -> dict:
         """The last LARS / clipping step's norms as Python values (synchronises): ``grad_norm`` (of
         the scaled gradient, before clipping), ``clip_coef``, and per tensor name ``p_norm``,
@@ -1070,6 +1081,11 @@ class VGGEngine(ScheduleTensors):
     def finish_step(self):
         self.steps_taken += 1
         self._eval_dirty = True
+        self.health_mark()
+
+    def finish_micro_step(self):
+        """End of a micro-step that only folded its gradients (gradient accumulation): the per-step
+        health snapshot alone.  No update ran, so ``steps_taken`` stays."""
         self.health_mark()
 
     # ------------------------------------------------------------------ per-step health

@@ -108,6 +108,41 @@ def sgd_segmented(p, g, buf, bmap, table, lr, momentum, wd, first, planes=None):
         planes[:, cov] = pl[:, cov]
 
 
+def grad_fold(acc, g, mode, offset=0, count=-1):
+    """kernels/grad_fold.hip over [offset, offset + count) of two flat fp32 arenas:
+    mode 0 store: acc = g   1 add: acc = acc + g   2 merge: g = acc + g (plain ``torch.add``)."""
+    for t in (acc, g):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError("grad_fold: acc and g must be float32 tensors")
+        if not t.is_contiguous():
+            raise ValueError("grad_fold: acc and g must be contiguous")
+    if acc.device != g.device:
+        raise ValueError("grad_fold: acc and g must be on one device")
+    if acc.numel() != g.numel():
+        raise ValueError("grad_fold: acc and g must have one length")
+    if mode not in (0, 1, 2):
+        raise ValueError("grad_fold: mode must be 0 (store), 1 (add) or 2 (merge)")
+    if offset < 0:
+        raise ValueError("grad_fold: offset must be >= 0")
+    if count < -1:
+        raise ValueError("grad_fold: count must be >= 0 (or -1: to the end)")
+    if offset > acc.numel():
+        raise ValueError("grad_fold: the slice ends past the arena")
+    if count < 0:
+        count = acc.numel() - offset
+    if offset % 4 or count % 4:
+        raise ValueError("grad_fold: offset and count must be multiples of 4")
+    if count > acc.numel() - offset:
+        raise ValueError("grad_fold: the slice ends past the arena")
+    a, b = acc.view(-1)[offset:offset + count], g.view(-1)[offset:offset + count]
+    if mode == 0:
+        a.copy_(b)
+    elif mode == 1:
+        torch.add(a, b, out=a)
+    else:
+        torch.add(a, b, out=b)
+
+
 def lr_advance(table, step, lr, host_pos, from_device):
     """kernels/lr_sched.hip: lr[0] = table[min(pos, T - 1)], step[0] = pos + 1, with pos the
     counter's value (from_device) or host_pos."""

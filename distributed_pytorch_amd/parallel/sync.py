@@ -26,7 +26,11 @@ Differences from the reference, all by design:
   (``params_free``: dgrad of that layer enqueued), the fused SGD of that slice is queued behind the
   collective on the comm stream, so only the small tail bucket's collective and update follow
   backward.  Per-element SGD math is unchanged, so results are bitwise identical to the default
-  single SGD launch after ``finish()`` — which measures faster on MI355X (see GradSync).
+  single SGD launch after ``finish()`` — which measures faster on MI355X (see GradSync);
+* gradient accumulation (``accum.AccumulatedStep``): ``begin_micro_step`` begins a step that only
+  folds its gradients into the engine's accumulator arena, bucket by bucket from ``grad_ready``,
+  and touches no communicator; ``begin_final_step`` begins the group's closing step, which merges
+  the accumulator into each bucket right before that bucket's collective.
 """
 from __future__ import annotations
 
@@ -42,7 +46,7 @@ from .comm import Comm
 
 
 class Bucket:
-    __slots__ = ("names", "lo", "hi", "pending", "issued", "busy", "stepped", "free_ev", "free_sig")
+    __slots__ = ("names", "lo", "hi", "pending", "issued", "busy", "stepped", "free_ev", "free_sig", "folded")
 
     def __init__(self, names: List[str], lo: int, hi: int):
         self.names = list(names)
@@ -51,6 +55,7 @@ class Bucket:
         self.busy = set(names)      # parameters still read by kernels not yet enqueued this step
         self.issued = False         # collective enqueued
         self.stepped = False        # optimizer step of this slice enqueued
+        self.folded = False         # gradient-accumulation fold of this slice enqueued (accumulated steps)
         self.free_ev = None         # main-stream event after the last reader of the parameters
         self.free_sig = None        # ... or a later main-stream kernel's start signal (flag, value)
 
@@ -155,6 +160,12 @@ class GradSync:
                           and type(self).reduce_bucket_here is not GradSync.reduce_bucket_here)
         self._joined = False
         self._main = None
+        # gradient accumulation (accumulate / begin_micro_step / begin_final_step): the fold every
+        # bucket gets in grad_ready this step (None: an ordinary step; 0 store, 1 add, 2 merge), and
+        # whether the step is a fold-only micro-step (no collective, no BN-buffer send, no update)
+        self._fold: Optional[int] = None
+        self._micro = False
+        self.accum_steps = 1
         # optional utils.profiling.EventProbe: marks b{i}_start / b{i}_end around each bucket's
         # collective on the comm stream (bench diagnostic phase only)
         self.probe = None
@@ -203,7 +214,86 @@ class GradSync:
         self._joined = False
         self._main = torch.cuda.current_stream(self.engine.device) if self._cuda else None
 
+    # -- gradient accumulation (accum.AccumulatedStep drives these) --
+    # One mechanism for every mode: the step's fold of a bucket (engine.grad_fold over its slice) is
+    # enqueued in grad_ready when the bucket's last tensor is reported, on the stream current there
+    # -- the stream and point behind which the bucket's collective is ordered in an ordinary step
+    # (the engine's drain_side() arrangement for the last bucket included), so the fold sees every
+    # producer of the bucket and runs under the rest of the backward.  In the merging final step the
+    # collective follows in the same call: comm.region() joins the comm stream behind the merge (the
+    # tail bucket's all-reduce is on that stream itself).  The engine's end-of-backward join orders
+    # the next micro-step's gradient writers behind every fold.
+    def accumulate(self, accum_steps: int):
+        """Declare that steps are accumulated over ``accum_steps`` > 1 micro-steps: the update is
+        then one whole-arena step after the closing micro-step's sync (DPA_FUSED_STEP is ignored,
+        as it is for LARS)."""
+        self.accum_steps = int(accum_steps)
+        if self.accum_steps > 1 and self.fuse_step:
+            if self.comm.rank == 0:
+                print(f"[sync] DPA_FUSED_STEP ignored: gradient accumulation ({self.accum_steps} micro-steps) "
+                      "updates after the closing micro-step's gradient sync", flush=True)
+            self.fuse_step = False
+
+    def begin_micro_step(self, first: bool):
+        """Begin a fold-only micro-step: ``gacc = grads`` (first of its group) or ``gacc += grads``
+        per bucket, and nothing else -- no communicator call, no BN-buffer send, no update."""
+        self._begin_folding(0 if first else 1, True)
+
+    def begin_final_step(self):
+        """Begin the closing micro-step of a group of more than one: ``grads = gacc + grads`` per
+        bucket, then the mode's ordinary sync of that bucket."""
+        self._begin_folding(2, False)
+
+    def _begin_folding(self, fold: int, micro: bool):
+        self.begin_step()
+        for b in self.buckets:
+            b.folded = False
+        self._fold, self._micro = fold, micro
+
+    def finish_micro_step(self):
+        """End of a fold-only micro-step (main stream, after the engine's end-of-backward join):
+        fold whatever grad_ready did not see complete."""
+        self._end_folding()
+
+    def _fold_buckets(self, buckets: List[Bucket]):
+        """The step's fold over these buckets' slices on the current stream: one launch per run of
+        adjacent slices (the per-tensor buckets of one layer are reported together and lie side by
+        side: one launch for the layer instead of four)."""
+        lo = hi = None
+        for b in sorted(buckets, key=lambda b: b.lo):
+            b.folded = True
+            if hi is not None and b.lo == hi:
+                hi = b.hi
+                continue
+            if hi is not None:
+                self.engine.grad_fold(self._fold, lo, hi - lo)
+            lo, hi = b.lo, b.hi
+        if hi is not None:
+            self.engine.grad_fold(self._fold, lo, hi - lo)
+
+    def _fold_ready(self, names: List[str]):
+        """grad_ready of an accumulated step: fold the buckets this report completes, here and now."""
+        done = []
+        for n in names:
+            b = self._by_name.get(n)
+            if b is None:
+                continue
+            b.pending.discard(n)
+            if not b.pending and not b.folded and b not in done:
+                done.append(b)
+        self._fold_buckets(done)
+
+    def _end_folding(self):
+        """Fold the buckets grad_ready did not see complete; the next step is an ordinary one again
+        unless it begins otherwise."""
+        self._fold_buckets([b for b in self.buckets if not b.folded])
+        self._fold, self._micro = None, False
+
     def grad_ready(self, names: List[str]):
+        if self._fold is not None:  # an accumulated step: the folds first, then the buckets' collectives
+            self._fold_ready(names)
+            if self._micro:
+                return
         for n in names:
             b = self._by_name.get(n)
             if b is None:
@@ -299,6 +389,8 @@ class GradSync:
     def finish(self) -> float:
         """Issue whatever is left, make the compute stream wait for the comm stream, and return
         the scale the optimizer must apply to the synced grads."""
+        if self._fold is not None:  # (a merging final step: buckets grad_ready did not see complete)
+            self._end_folding()
         if not self.active:
             if self.fuse_step and self._cuda and self.engine.wstream is not None:
                 self._join(torch.cuda.current_stream(self.engine.device), self.engine.wstream)
@@ -402,7 +494,9 @@ class DDPSync(GradSync):
         self._bufs_sent = self._bufs_fresh = True
 
     def _post_forward_send(self) -> bool:
-        return self.active and self.broadcast_buffers and not self._bufs_sent
+        # (a fold-only micro-step of an accumulated step sends nothing: the group's closing
+        # micro-step broadcasts rank 0's statistics, where an ordinary step does)
+        return self.active and self.broadcast_buffers and not self._bufs_sent and not self._micro
 
     def begin_step(self):
         super().begin_step()
@@ -428,7 +522,7 @@ class DDPSync(GradSync):
         return super().finish()
 
     def pre_forward(self):
-        if not self.active or not self.broadcast_buffers:
+        if not self.active or not self.broadcast_buffers or self._micro:
             return None
         if self._bufs_fresh:  # already broadcast after the previous training forward
             self._bufs_fresh = False

@@ -23,6 +23,7 @@ from typing import Optional
 
 import torch
 
+from .accum import AccumulatedStep, updates_per_epoch, validate_args
 from .data import DeviceLoader, ShardSampler, get_datasets
 from .engine import VGGEngine
 from .graph_step import GraphedStep
@@ -102,10 +103,20 @@ def train_model(engine: VGGEngine, loader: DeviceLoader, sync, epoch: int, ctx: 
     ck_every = getattr(args, "checkpoint_every", 0) or 0
     graphed = GraphedStep(engine, sync) if getattr(args, "graph", False) and not sync.active and dev.type == "cuda" \
         else None
+    # gradient accumulation (--accum-steps A > 1): groups of A loader batches in index order, one
+    # update per group; a group also ends with the epoch or at --max-iters.  Checkpoints and
+    # --stop-after-iters act only where a group ended.
+    A = getattr(args, "accum_steps", 1) or 1
+    accum = AccumulatedStep(engine, sync, A) if A > 1 else None
+    n_batches = len(loader)
     for batch_idx, (x, target) in enumerate(loader.iterate(start_batch), start=start_batch):
+        closed = True
         if graphed is not None:
             with trace_range("step_graph"):
                 graphed.run(x, target)
+        elif accum is not None:
+            closed = accum.run(x, target, last=batch_idx + 1 >= n_batches
+                               or bool(max_iters and n_iters + 1 >= max_iters))
         else:
             _eager_step(engine, sync, x, target)
         n_iters += 1
@@ -135,10 +146,12 @@ def train_model(engine: VGGEngine, loader: DeviceLoader, sync, epoch: int, ctx: 
             agreed_health_check(engine, ctx)  # never save weights built from a failed step, on any rank
             sync.prepare_checkpoint()
             checkpoint.save(args.checkpoint_dir, ctx.rank, engine, epoch, batch_idx + 1, args.sampler_seed, ctx.world,
-                            sync.mode, ddp_prefix=sync.mode == "ddp")
+                            sync.mode, ddp_prefix=sync.mode == "ddp", accum_steps=A)
         if max_iters and n_iters >= max_iters:
             break
-        if budget is not None and n_iters >= budget and batch_idx + 1 < len(loader):
+        # (accumulating: the budget, a multiple of A, can run out inside a group when an earlier
+        # epoch ended with a short one; the run then stops where this group ends)
+        if budget is not None and n_iters >= budget and closed and batch_idx + 1 < len(loader):
             stopped_at = batch_idx + 1
             break
     _sync(dev)
@@ -236,6 +249,10 @@ def add_common_args(ap: argparse.ArgumentParser):
     g.add_argument("--stop-after-iters", type=int, default=None,
                    help="end the whole run after this many training iterations, mid-epoch if need be, writing a "
                         "resumable checkpoint (preemption drill for --resume)")
+    g.add_argument("--accum-steps", type=int, default=1, metavar="A",
+                   help="gradient accumulation: one update per group of A loader batches (effective batch A x "
+                        "world x --batch-size); micro-steps before a group's last run no collective; schedules, "
+                        "--warmup-iters and the LARS / clipping norms count and see updates (default: 1 = off)")
     g.add_argument("--no-eval", action="store_true")
     g.add_argument("--trace", action="store_true", help="emit roctx ranges (rocprofv3 --marker-trace)")
     g.add_argument("--profile", action="store_true",
@@ -261,7 +278,8 @@ def resume(ctx: DistContext, engine: VGGEngine, mode: str, args, n_batches: int)
     err, obj = None, None
     try:
         obj = checkpoint.load(args.checkpoint_dir, ctx.rank, engine, world=ctx.world, mode=mode,
-                              reshard=getattr(args, "resume_reshard", False))
+                              reshard=getattr(args, "resume_reshard", False),
+                              accum_steps=getattr(args, "accum_steps", 1) or 1)
         point = checkpoint.resume_point(obj)
     except checkpoint.ResumeMismatch as e:
         err, point = e, (-1, -1, -1, -1)
@@ -287,6 +305,7 @@ def build_engine(args, device) -> VGGEngine:
 
 
 def run(ctx: DistContext, mode: str, args):
+    A = validate_args(args)
     if args.trace:
         enable_tracing(True)
     torch.manual_seed(args.seed)  # main.py:70 — identical init on all ranks (plus a rank-0 broadcast)
@@ -301,9 +320,10 @@ def run(ctx: DistContext, mode: str, args):
     engine.init_parameters(seed=args.seed)
     if train_loader.mix is not None:  # Mixup / CutMix: the training loss takes the loader's pair targets
         engine.set_mix(*train_loader.mix)
-    # the schedule covers epochs x (this rank's iterations per epoch); set before resume(), which
-    # checks the checkpoint's schedule against it and restores its position (steps_taken)
-    table = table_from_args(args, min(len(train_loader), args.max_iters or len(train_loader)))
+    # the schedule covers epochs x (this rank's updates per epoch: its iterations, or its groups of
+    # --accum-steps iterations); set before resume(), which checks the checkpoint's schedule against
+    # it and restores its position (steps_taken)
+    table = table_from_args(args, updates_per_epoch(len(train_loader), args.max_iters, A))
     if table is not None:
         engine.set_lr_schedule(table)
     start_epoch, start_batch = resume(ctx, engine, mode, args, len(train_loader))
@@ -322,12 +342,12 @@ def run(ctx: DistContext, mode: str, args):
             if args.checkpoint_dir:
                 sync.prepare_checkpoint()
                 checkpoint.save(args.checkpoint_dir, ctx.rank, engine, epoch, stopped, args.sampler_seed, ctx.world,
-                                mode, ddp_prefix=mode == "ddp")
+                                mode, ddp_prefix=mode == "ddp", accum_steps=A)
             break
         if args.checkpoint_dir:
             sync.prepare_checkpoint()
             checkpoint.save(args.checkpoint_dir, ctx.rank, engine, epoch + 1, 0, args.sampler_seed, ctx.world, mode,
-                            ddp_prefix=mode == "ddp")
+                            ddp_prefix=mode == "ddp", accum_steps=A)
         res = None
         if not args.no_eval:
             res = test_model(engine, test_loader, sync)
@@ -345,6 +365,8 @@ def run(ctx: DistContext, mode: str, args):
             for k in ("mixup", "cutmix"):  # train_loss is then the pair-target loss of the mixed batches
                 if getattr(args, k, 0.0):
                     rec[k] = getattr(args, k)
+            if A > 1:  # one update per A iterations; the throughput figures stay per loader batch
+                rec["accum_steps"], rec["effective_batch"] = A, A * ctx.world * args.batch_size
             if engine.lr_spec is not None:  # the rate of the epoch's last step
                 rec["lr"], rec["lr_schedule"] = engine.current_lr(), engine.lr_spec
             if engine.whole_arena_step and engine.steps_taken > 0:  # the epoch's last step
@@ -378,6 +400,7 @@ def main_cli(mode: str, argv=None):
     ap.add_argument("--rank", required=True, type=int)
     add_common_args(ap)
     args = ap.parse_args(argv)
+    validate_args(args)  # before anything touches a device
     rc = _maybe_profile(args, argv)
     if rc is not None:
         raise SystemExit(rc)
@@ -390,6 +413,7 @@ def main_env(mode: str = "ddp", argv=None):
     ap = argparse.ArgumentParser(prog="Input arguments", description="gather ip, nunber of workers, rank")
     add_common_args(ap)
     args = ap.parse_args(argv)
+    validate_args(args)  # before anything touches a device
     rc = _maybe_profile(args, argv)
     if rc is not None:
         raise SystemExit(rc)
@@ -403,6 +427,7 @@ def main_single(argv=None):
     ap = argparse.ArgumentParser(prog="main.py")
     add_common_args(ap)
     args = ap.parse_args(argv)
+    validate_args(args)  # before anything touches a device
     rc = _maybe_profile(args, argv)
     if rc is not None:
         raise SystemExit(rc)

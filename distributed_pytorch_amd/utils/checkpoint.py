@@ -9,6 +9,8 @@ Layout: ``<dir>/rank{R}.pt`` holding
      "world": int, "mode": str, "steps_taken": int, "rng": torch CPU RNG state}
     + "lr_schedule": the schedule's spec dict, only when the engine has a learning-rate schedule
       (its position is ``steps_taken``; ``optimizer`` keeps the base rate)
+    + "accum_steps": A, only when gradients are accumulated over A > 1 batches (``batch_idx`` is then
+      a boundary of the groups; a run with another A refuses the file)
 
 ``model`` loads straight into ``model.VGG11().load_state_dict`` (after stripping ``module.``).
 Loading uses ``torch.load(weights_only=True)`` — nothing in the file is executed.
@@ -44,7 +46,7 @@ def path_for(ckpt_dir: str, rank: int) -> str:
 
 
 def save(ckpt_dir: str, rank: int, engine, epoch: int, batch_idx: int, sampler_seed: int = 0, world: int = 1,
-         mode: str = "single", ddp_prefix: bool = False) -> str:
+         mode: str = "single", ddp_prefix: bool = False, accum_steps: int = 1) -> str:
     os.makedirs(ckpt_dir, exist_ok=True)
     obj = {
         "model": engine.state_dict(prefix="module." if ddp_prefix else ""),
@@ -60,6 +62,8 @@ def save(ckpt_dir: str, rank: int, engine, epoch: int, batch_idx: int, sampler_s
     spec = getattr(engine, "lr_spec", None)
     if spec is not None:  # a learning-rate schedule: its position is steps_taken, nothing else is state
         obj["lr_schedule"] = spec
+    if int(accum_steps) > 1:  # gradient accumulation: batch_idx is then a boundary of groups of this length
+        obj["accum_steps"] = int(accum_steps)
     p = path_for(ckpt_dir, rank)
     tmp = p + ".tmp"
     torch.save(obj, tmp)
@@ -68,10 +72,10 @@ def save(ckpt_dir: str, rank: int, engine, epoch: int, batch_idx: int, sampler_s
 
 
 def load(ckpt_dir: str, rank: int, engine, map_location="cpu", world: Optional[int] = None,
-         mode: Optional[str] = None, reshard: bool = False) -> Optional[dict]:
+         mode: Optional[str] = None, reshard: bool = False, accum_steps: int = 1) -> Optional[dict]:
     """Load rank's checkpoint into ``engine``; returns the checkpoint dict (with ``batch_idx``
-    reset to 0 when resharding) or None if there is none.  ``world`` / ``mode``: the current run's,
-    validated against the saved ones."""
+    reset to 0 when resharding) or None if there is none.  ``world`` / ``mode`` / ``accum_steps``:
+    the current run's, validated against the saved ones."""
     p = path_for(ckpt_dir, rank)
     if not os.path.exists(p):
         if not reshard:
@@ -104,6 +108,14 @@ def load(ckpt_dir: str, rank: int, engine, map_location="cpu", world: Optional[i
         raise ResumeMismatch(f"{p} was written with the learning-rate schedule {saved_s}, this run has {cur_s}: "
                              "the saved step count would index another schedule. Resume with the schedule options "
                              "of the run that wrote the checkpoint.")
+    saved_a, cur_a = int(obj.get("accum_steps", 1)), int(accum_steps)
+    if saved_a != cur_a:
+        raise ResumeMismatch(f"{p} was written with --accum-steps {saved_a}, this run has {cur_a}: its step count "
+                             "and batch position belong to groups of another length. Resume with the "
+                             "--accum-steps of the run that wrote the checkpoint.")
+    if int(obj["batch_idx"]) % cur_a:
+        raise ResumeMismatch(f"{p} stands at batch {obj['batch_idx']}, inside a group of {cur_a} accumulated "
+                             "micro-batches: the gradients folded before it were not saved")
     engine.load_state_dict(obj["model"])
     engine.load_optimizer_state_dict(obj["optimizer"])
     if "steps_taken" in obj:
