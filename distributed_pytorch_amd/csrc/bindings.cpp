@@ -1,122 +1,14 @@
 // Python bindings for the gfx950 kernels and the native RCCL communicator.
-// Thin: validate tensors, fetch the caller's current HIP stream, call the extern "C" launchers.
+// Thin: validate tensors, fetch the caller's current HIP stream, call the extern "C" launchers (kernels/api.h).
 #include <c10/hip/HIPStream.h>
 #include <c10/hip/HIPCachingAllocator.h>
 #include <torch/extension.h>
 
-#include "kernels/optim_api.h"
+#include "kernels/api.h"
+#include "kernels/ipc_coll.h"
 #include "runtime/ipc_comm.h"
 #include "runtime/rccl_comm.h"
 #include "runtime/tcp_store.h"
-
-extern "C" {
-int dpa_spin(long long usec, int* done, hipStream_t s);
-int dpa_mean_of_w(const float* in, float* out, long n, int W, hipStream_t s);
-int dpa_add_inplace(void* out, const void* add, long n, int bf, hipStream_t s);
-int dpa_conv_fprop(const float* x, const float* w, float* out, float* slab, int N, int H, int W, int C, int Kout,
-                   int R, int S, int stride, int pad, int splits, int tile, int dgrad, int reduce, int posmajor,
-                   hipStream_t st);
-int dpa_conv_splits(int Kred, int splits);
-int dpa_conv_wgrad(const float* x, const float* dz, float* dw, float* slab, int N, int H, int W, int C, int Kout,
-                   int R, int S, int stride, int pad, int splits, int tile, int posmajor, hipStream_t st);
-int dpa_wflip(const float* w, float* wd, int K, int R, int S, int C, hipStream_t st);
-long dpa_bn_part_floats(int M, int C, int bwd);
-int dpa_bn_fwd_stats(const void* src, int nsplit, void* z, float* part, int M, int C, const float* gamma,
-                     const float* beta, const float* bias, float* rmean, float* rvar, long long* nbt, float* mean,
-                     float* invstd, float* scale, float* shift, float momentum, float eps, int zbf, hipStream_t st);
-int dpa_bn_eval_params(const float* gamma, const float* beta, const float* bias, const float* rmean,
-                       const float* rvar, float* scale, float* shift, int C, float eps, hipStream_t st);
-int dpa_bn_apply(const void* z, float* a, unsigned short* a3, int np, const float* scale, const float* shift, int N,
-                 int H, int W, int C, int pool, int act, const void* res, int zbf, hipStream_t st,
-                 unsigned char* mask);
-int dpa_bn_bwd(const void* gsrc, int nsplit, void* g, const void* z, const float* scale, const float* shift,
-               const float* mean, const float* invstd, const float* gamma, float* part, float* coef, float* dgamma,
-               float* dbeta, float* dbias, float* dz, unsigned short* dz3, int np, int N, int H, int W, int C,
-               int pool, int act, const void* res, void* dres, int zbf, hipStream_t st, int* sig, int sig_val,
-               const void* g2, const unsigned char* mask, unsigned* bound);
-long dpa_wgrad0_part_floats(int N);
-int dpa_gap(const void* x, float* feat, int N, int HW, int C, int xbf, hipStream_t st);
-int dpa_ce(const float* logits, const long long* target, float* loss_row, float* dlogits, int* correct_row,
-           float* loss, float* acc, int N, int J, hipStream_t st, float label_smoothing, const long long* target2,
-           const float* lam);
-int dpa_head_bwd_prep(const float* dlogits, const float* gout, float* dl, float* db, int N, int J, hipStream_t st);
-int dpa_gap_bwd(const float* dfeat, void* dx, int N, int HW, int C, int xbf, hipStream_t st);
-long dpa_conv0_part_floats(int N);
-int dpa_gemm_f32(const float* A, int lda, int ak, const float* B, int ldb, int bk, float* C, int M, int N, int K,
-                 const float* bias, float* slab, int splits, hipStream_t st);
-int dpa_conv0_fwd(const float* x, const float* w, int CP, float* z, float* part, int N, const float* gamma,
-                  const float* beta, const float* bias, float* rmean, float* rvar, long long* nbt, float* mean,
-                  float* invstd, float* scale, float* shift, float momentum, float eps, hipStream_t st);
-int dpa_bn_bwd_wgrad0(const float* gsrc, int nsplit, float* g, const float* z, const float* scale,
-                      const float* shift, const float* mean, const float* invstd, const float* gamma, float* part,
-                      float* coef, float* dgamma, float* dbeta, float* dbias, const float* x, float* wpart,
-                      float* dw, int CP, int N, hipStream_t st, int* sig, int sig_val);
-int dpa_fc_ce_train(const float* x, const float* w, const float* b, const long long* target, float* loss_row,
-                    float* dlogits, float* dx, float* dw, float* db, float* loss_out, float* loss_accum, int B,
-                    int Cin, int J, hipStream_t st, const float* bn_z, const float* bn_scale,
-                    const float* bn_shift, int parts, float label_smoothing, const long long* target2,
-                    const float* lam);
-int dpa_fc_ce_eval(const float* x, const float* w, const float* b, const long long* target, float* loss_row,
-                   int* correct_row, float* logits, float* acc, int B, int Cin, int J, hipStream_t st);
-int dpa_x3_splits(int Kred, int splits);
-int dpa_conv_x3_fprop(const unsigned short* x, long xps, const unsigned short* w, long wps, void* out, float* slab,
-                      int N, int H, int W, int C, int Kout, int R, int S, int stride, int pad, int splits, int tile,
-                      int reduce, int posmajor, int np, int obf, hipStream_t st, float* stats, float oscale,
-                      const unsigned* obound);
-int dpa_conv_stats_rows(int tile);
-long dpa_ipc_slice(long n, int world);
-int dpa_bn_finalize_cm(const float* part, int nblk, int rpb, int M, int C, const float* gamma, const float* beta,
-                       const float* bias, float* rmean, float* rvar, long long* nbt, float* mean, float* invstd,
-                       float* scale, float* shift, float momentum, float eps, hipStream_t st);
-int dpa_conv_x3_wgrad(const unsigned short* x, long xps, const unsigned short* dz, long dzps, float* dw, float* slab,
-                      int N, int H, int W, int C, int Kout, int R, int S, int stride, int pad, int splits, int tile,
-                      int posmajor, int np, hipStream_t st, float oscale, const unsigned* obound);
-int dpa_split_planes(const float* x, unsigned short* out, long n, long ps, int np, float scale, hipStream_t st);
-int dpa_h2_ovf_conv(int clear);
-int dpa_h2_ovf_bn(int clear);
-int dpa_h2_ovf_sgd(int clear);
-int dpa_h2_ovf_fused(int clear);
-int dpa_h2_ovf_lars(int clear);
-int dpa_pad_split8(const float* x, unsigned short* out, long npix, int cin, long ps, int np, hipStream_t st);
-int dpa_conv_x3_dgrad(const unsigned short* dz, long dzps, const unsigned short* w, long wps, void* dx, float* slab,
-                      int N, int Hd, int Wd, int K, int C, int R, int S, int stride, int pad, int H, int W, int splits,
-                      int tile, int reduce, int posmajor, int np, int obf, hipStream_t st, const void* add, int* sig,
-                      int sig_val, float oscale, const unsigned* obound);
-int dpa_wait_signal(const int* sig, int val, long long timeout_us, int* tmo, hipStream_t st);
-int dpa_bn_fused_geo(int Mo, int C, int pool, int bwd, int rmax, long* part_floats, long* cnt_words, int* blocks);
-int dpa_bn_fused_fwd(const float* src, int nsplit, float* zw, int N, int H, int W, int C, int pool, int rmax,
-                     float* part, unsigned* cnt, const float* gamma, const float* beta, const float* bias,
-                     float* rmean, float* rvar, long long* nbt, float* mean, float* invstd, float* scale,
-                     float* shift, int apply, float* out, unsigned short* out3, int np, long ps, float momentum,
-                     float eps, int* tmo, long long timeout_us, hipStream_t st);
-int dpa_bn_fused_bwd(const float* gsrc, int nsplit, const float* z, int N, int H, int W, int C, int pool, int rmax,
-                     float* part, unsigned* cnt, const float* scale, const float* shift, const float* mean,
-                     const float* invstd, const float* gamma, float* dgamma, float* dbeta, float* dbias, float* out,
-                     unsigned short* out3, int np, long ps, int* tmo, long long timeout_us, hipStream_t st, int* sig,
-                     int sig_val);
-
-int dpa_set_signal(int* sig, int val, hipStream_t st);
-int dpa_health_copy(const int* const* w, int n, int* out, int tag, hipStream_t st);
-int* dpa_h2_ovf_conv_addr();
-int* dpa_h2_ovf_bn_addr();
-int* dpa_h2_ovf_sgd_addr();
-int* dpa_h2_ovf_fused_addr();
-int* dpa_h2_ovf_lars_addr();
-int dpa_bn_apply_wide(const unsigned short* z, const unsigned short* res, unsigned short* out, unsigned char* mask,
-                      const float* scale, const float* shift, long M, int C, int act, hipStream_t st,
-                      const float* rscale, const float* rshift);
-int dpa_maxpool_fwd(const void* x, void* y, unsigned char* arg, int N, int H, int W, int C, int k, int s, int p,
-                    int bf, hipStream_t st, const float* scale, const float* shift);
-int dpa_maxpool_bwd(const void* dy, const unsigned char* arg, void* dx, int N, int H, int W, int C, int k, int s,
-                    int p, int bf, hipStream_t st);
-int dpa_augment(const unsigned char* img, const long long* idx, const long long* labels, float* out,
-                long long* target, int B, int Hs, int Ws, int pad, int train, unsigned long long seed,
-                unsigned long long salt, const float* mean, const float* std, hipStream_t st);
-int dpa_augment_mix(const unsigned char* img, const long long* idx, const long long* labels, float* out,
-                    long long* target, long long* target2, float* lam_out, int mode, float lam, int y0, int y1,
-                    int x0, int x1, int B, int Hs, int Ws, int pad, unsigned long long seed, unsigned long long salt,
-                    const float* mean, const float* std, hipStream_t st);
-}
 
 namespace {
 

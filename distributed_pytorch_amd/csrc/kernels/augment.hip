@@ -7,6 +7,7 @@
 // out: fp32 NHWC [B][Hs][Ws][4] (channel 3 zero: the first conv is run with C padded to 4).
 // Per-sample crop offsets / flip come from a counter-based hash of (seed, sample index, salt),
 // so the stream is reproducible and independent of launch geometry.
+#include "api.h"
 #include "common.h"
 
 namespace {
@@ -132,8 +133,6 @@ __global__ __launch_bounds__(256) void augment_mix_kernel(const unsigned char* _
 
 }  // namespace
 
-// mode 0 = Mixup (the box is ignored), 1 = CutMix (box [y0,y1) x [x0,x1) inside the image; lam is only
-// stored).  Training augmentation only.  -2: a mode, lambda or box out of range.
 extern "C" int dpa_augment_mix(const unsigned char* img, const long long* idx, const long long* labels, float* out,
                                long long* target, long long* target2, float* lam_out, int mode, float lam, int y0,
                                int y1, int x0, int x1, int B, int Hs, int Ws, int pad, unsigned long long seed,

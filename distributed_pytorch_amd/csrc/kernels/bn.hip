@@ -25,24 +25,12 @@
 // in registers, combines them with an LDS tree, and writes ONE partial per (block, channel) —
 // deterministic, no atomics.  ~256 blocks: one wave of full CUs, few partials to merge.  The
 // backward reduce uses RTB (256) -thread blocks, ~512 of them (see RTB).
+#include "api.h"
 #include "common.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
-
-extern "C" {  // bn_wide.hip: bf16 apply passes with 16-byte lanes (return 1: not applicable)
-int dpa_bn_apply_wide(const unsigned short* z, const unsigned short* res, unsigned short* out, unsigned char* mask,
-                      const float* scale, const float* shift, long M, int C, int act, hipStream_t st,
-                      const float* rscale, const float* rshift);
-int dpa_bn_bwd_apply_wide(const unsigned short* g, const unsigned short* g2, const unsigned short* z,
-                          unsigned short* dz, const float* scale, const float* shift, const float* coef, long M, int C,
-                          int act, hipStream_t st);
-int dpa_bn_bwd_reduce_wide(const unsigned short* g, const unsigned short* g2, const unsigned short* z,
-                           const unsigned short* res, const unsigned char* mask, unsigned short* dyout,
-                           const float* scale, const float* shift, const float* mean, const float* invstd,
-                           float* part, int Mo, int C, int act, int rpb, int* sig, int sig_val, hipStream_t st);
-}
 
 namespace {
 
@@ -1339,10 +1327,7 @@ int bn_bwd_host(const TZ* gsrc, int nsplit, TZ* g, const TZ* z, const float* sca
 
 }  // namespace
 
-extern "C" {
-// floats of partial workspace needed by fwd stats (2 per (block, channel)) / bwd (5 per ...)
-// (backward: rows of the fp32 or the bf16 geometry, whichever has more; the bf16 wide reduce of
-// bn_wide.hip uses the bf16 geometry's rows per block)
+extern "C" {  // arguments: api.h
 long dpa_bn_part_floats(int M, int C, int bwd) {
   if (!bwd) {
     const int rpb = red_rows_per_block(M, C);
@@ -1354,8 +1339,6 @@ long dpa_bn_part_floats(int M, int C, int bwd) {
   return std::max((long)((M + r32 - 1) / r32) * 8, (long)((M + r16 - 1) / r16) * 5) * C;
 }
 
-// z [M][C] (or nsplit fp32 slabs of it in src; then z is written) -> partials -> finalize.
-// zbf: z/src are bf16 (nsplit must be 1).
 int dpa_bn_fwd_stats(const void* src, int nsplit, void* z, float* part, int M, int C, const float* gamma,
                      const float* beta, const float* bias, float* rmean, float* rvar, long long* nbt, float* mean,
                      float* invstd, float* scale, float* shift, float momentum, float eps, int zbf, hipStream_t st) {
@@ -1367,8 +1350,6 @@ int dpa_bn_fwd_stats(const void* src, int nsplit, void* z, float* part, int M, i
                                   nbt, mean, invstd, scale, shift, momentum, eps, st);
 }
 
-// Finalize from (mean, M2) partials of nblk row blocks of rpb rows each (the producer is not
-// bn_stats_kernel, e.g. the first-layer conv's epilogue, first_layer.hip).
 int dpa_bn_finalize(const float* part, int nblk, int rpb, int M, int C, const float* gamma, const float* beta,
                     const float* bias, float* rmean, float* rvar, long long* nbt, float* mean, float* invstd,
                     float* scale, float* shift, float momentum, float eps, hipStream_t st) {
@@ -1377,7 +1358,6 @@ int dpa_bn_finalize(const float* part, int nblk, int rpb, int M, int C, const fl
   return (int)hipGetLastError();
 }
 
-// Finalize from channel-major partials part[c][k] (conv epilogue statistics).
 int dpa_bn_finalize_cm(const float* part, int nblk, int rpb, int M, int C, const float* gamma, const float* beta,
                        const float* bias, float* rmean, float* rvar, long long* nbt, float* mean, float* invstd,
                        float* scale, float* shift, float momentum, float eps, hipStream_t st) {
@@ -1392,8 +1372,6 @@ int dpa_bn_eval_params(const float* gamma, const float* beta, const float* bias,
   return (int)hipGetLastError();
 }
 
-// out: fp32 a (np == 0), bf16 planes a3 [np][...] (np in {1, 3}) or fp16 pairs (np 2, scale H2_SA).  act: 0 relu (pool allowed),
-// 1 none, 2 relu(. + res).  zbf: z and res are bf16.
 int dpa_bn_apply(const void* z, float* a, u16* a3, int np, const float* scale, const float* shift, int N, int H,
                  int W, int C, int pool, int act, const void* res, int zbf, hipStream_t st, unsigned char* mask) {
   if (C % 4 || act < 0 || act > 2 || (act != 0 && pool) || (act == 2 && !res)) return -2;
@@ -1405,10 +1383,6 @@ int dpa_bn_apply(const void* z, float* a, u16* a3, int np, const float* scale, c
                               mask);
 }
 
-// gsrc: grad of the layer output (pooled shape if pool), or nsplit fp32 slabs of it (then the sum is
-// written to g).  Writes dz [N,H,W,C] (fp32, or bf16 planes dz3) and dgamma/dbeta/dbias; act 2 also
-// the residual gradient dres.  zbf: gsrc/g/z/res/dres are bf16 (nsplit must be 1).  g2 (optional,
-// same type and shape as g, nsplit 1): the gradient is gsrc + g2, summed on load.
 int dpa_bn_bwd(const void* gsrc, int nsplit, void* g, const void* z, const float* scale, const float* shift,
                const float* mean, const float* invstd, const float* gamma, float* part, float* coef, float* dgamma,
                float* dbeta, float* dbias, float* dz, u16* dz3, int np, int N, int H, int W, int C, int pool, int act,
@@ -1427,8 +1401,6 @@ int dpa_bn_bwd(const void* gsrc, int nsplit, void* g, const void* z, const float
                             (float*)dres, st, sig, sig_val, (const float*)g2, mask, bound);
 }
 
-// Layer-0 backward (see bn_bwd_wgrad0_kernel): BN statistics, then the fused apply + weight gradient.
-// g [N,16,16,64] (or nsplit slabs of it in gsrc), z [N,32,32,64], x [N,32,32,4] fp32, dw [64,3,3,CP].
 long dpa_wgrad0_part_floats(int N) { return (long)N * (16 / WB0_RPB) * 64 * 27; }
 
 int dpa_bn_bwd_wgrad0(const float* gsrc, int nsplit, float* g, const float* z, const float* scale,

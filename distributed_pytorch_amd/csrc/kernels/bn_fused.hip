@@ -35,6 +35,7 @@
 // stream's kernels hold the rest of the chip.  A block that waits longer than `ticks` of the wall clock (the
 // engine's own short bound, DPA_BN_FUSED_TIMEOUT_US, 2 s by default) sets tmo[0] = 1 and continues
 // (garbage, never a hang; the engine raises on the word after the step).
+#include "api.h"
 #include "common.h"
 
 namespace {
@@ -659,9 +660,7 @@ int test_phantom() {
 
 }  // namespace
 
-extern "C" {
-// Geometry query: 0 when the one-launch BN runs this layer (Mo row units of C channels) with at most
-// rmax row blocks per channel slice; writes the workspace floats and counter words it needs.
+extern "C" {  // arguments: api.h
 int dpa_bn_fused_geo(int Mo, int C, int pool, int bwd, int rmax, long* part_floats, long* cnt_words, int* blocks) {
   Geo g;
   if (!pick_geo_resident(Mo, C, pool != 0, bwd != 0, rmax, g)) return -6;
@@ -671,9 +670,6 @@ int dpa_bn_fused_geo(int Mo, int C, int pool, int bwd, int rmax, long* part_floa
   return 0;
 }
 
-// Forward: src = z [N,H,W,C] fp32 or nsplit slabs of it (z is then written to zw); writes mean,
-// invstd, scale, shift, the running statistics and nbt, and (apply != 0) relu(BN(z)) [2x2 pooled]
-// as fp32 out or bf16 planes out3 [np][...] (plane stride ps).
 int dpa_bn_fused_fwd(const float* src, int nsplit, float* zw, int N, int H, int W, int C, int pool, int rmax,
                      float* part, unsigned* cnt, const float* gamma, const float* beta, const float* bias,
                      float* rmean, float* rvar, long long* nbt, float* mean, float* invstd, float* scale,
@@ -700,8 +696,6 @@ int dpa_bn_fused_fwd(const float* src, int nsplit, float* zw, int N, int H, int 
   return g.CL == 16 ? dispatch<16>(false, pool != 0, np, g, a, st) : dispatch<8>(false, pool != 0, np, g, a, st);
 }
 
-// Backward: gsrc = dL/d(layer output) [N,Ho,Wo,C] fp32 or nsplit slabs of it; z, scale, shift, mean,
-// invstd from the forward; writes dgamma, dbeta, dbias and dz (fp32 out or bf16 planes out3).
 int dpa_bn_fused_bwd(const float* gsrc, int nsplit, const float* z, int N, int H, int W, int C, int pool, int rmax,
                      float* part, unsigned* cnt, const float* scale, const float* shift, const float* mean,
                      const float* invstd, const float* gamma, float* dgamma, float* dbeta, float* dbias, float* out,

@@ -9,6 +9,7 @@
 //
 // Grid: a grid stride that is a multiple of C/8 keeps each thread on one channel group (its
 // coefficients loaded once); four (forward) or two (backward) rows' loads in flight per thread.
+#include "api.h"
 #include "common.h"
 
 namespace {
@@ -281,11 +282,7 @@ bool wide_red_on() {
 
 }  // namespace
 
-extern "C" {
-// Backward reduce for bf16, unpooled, unsplit tensors in bn.hip's 1024-thread geometry: rpb is
-// bn.hip's rows per block (rounded up here to whole iterations, so the grid never exceeds its and
-// the partial workspace fits).  Returns the number of blocks launched (the finalize's partial
-// rows), 0 when not applicable (the caller runs bn.hip's kernel), or -(HIP error).
+extern "C" {  // arguments: api.h
 int dpa_bn_bwd_reduce_wide(const unsigned short* g, const unsigned short* g2, const unsigned short* z,
                            const unsigned short* res, const unsigned char* mask, unsigned short* dyout,
                            const float* scale, const float* shift, const float* mean, const float* invstd,
@@ -314,9 +311,6 @@ int dpa_bn_bwd_reduce_wide(const unsigned short* g, const unsigned short* g2, co
   return e ? -e : nblk;
 }
 
-// bf16 [M][C] -> bf16 [M][C] (+ mask [M*C/4] bytes for act 2); returns 1 when not applicable (the
-// caller runs bn.hip's kernel), else a HIP error code.  rscale / rshift (act 2 only): the residual is a
-// BatchNorm input, added as bf16(fma(res, rscale, rshift)) (bn_apply_wide_kernel RBN).
 int dpa_bn_apply_wide(const unsigned short* z, const unsigned short* res, unsigned short* out, unsigned char* mask,
                       const float* scale, const float* shift, long M, int C, int act, hipStream_t st,
                       const float* rscale, const float* rshift) {
@@ -342,8 +336,6 @@ int dpa_bn_apply_wide(const unsigned short* z, const unsigned short* res, unsign
   return (int)hipGetLastError();
 }
 
-// backward apply, bf16: g (+ g2) and z [M][C] -> dz [M][C]; act 0 (ReLU) or 1 (identity); returns 1
-// when not applicable
 int dpa_bn_bwd_apply_wide(const unsigned short* g, const unsigned short* g2, const unsigned short* z,
                           unsigned short* dz, const float* scale, const float* shift, const float* coef, long M, int C,
                           int act, hipStream_t st) {

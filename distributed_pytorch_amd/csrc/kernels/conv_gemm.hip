@@ -27,6 +27,7 @@
 //
 // LDS images: a k-contiguous operand is stored [row][BK+4] (16-row b128 lane groups hit 16
 // distinct 16-B slots: conflict-free), a row-contiguous operand (WGRAD A/B, DGRAD B) [BK][rows+4].
+#include "api.h"
 #include "common.h"
 
 namespace {
@@ -505,9 +506,7 @@ int set_ranges(ConvArgs& a, long xelems, long welems) {
 }
 }  // namespace
 
-extern "C" {
-
-// effective split count the launcher will use for a reduction of `ntiles_k` BK-tiles
+extern "C" {  // arguments: api.h
 int dpa_conv_splits(int Kred, int splits) {
   const int nt = cdiv(Kred, BK);
   if (splits < 1) splits = 1;
@@ -515,13 +514,6 @@ int dpa_conv_splits(int Kred, int splits) {
   return splits < 1 ? 1 : splits;
 }
 
-// Forward conv (and, with dgrad=1, the stride-1 "same" data-gradient conv reading the ORIGINAL
-// weights with flipped taps).  x: NHWC [N,H,W,C]; w: fprop [Kout][R][S][C], dgrad [C][R][S][Kout]
-// (the original conv's weights, whose input channels Kout are this GEMM's outputs); out
-// [N,P,Q,Kout].  splits > 1: partial sums go to slab[splits][N,P,Q,Kout]; reduce=1 sums them into
-// out here, reduce=0 leaves them for a consumer that sums on the fly (bn_fwd_stats / bn_bwd).
-// tile: 0 -> 128x128 (4 waves, 64x64 each), 1 -> 64x64 (4 waves, 32x32 each)
-// posmajor: position-major row order + tap skipping (any value is correct; 1 is faster on small maps)
 int dpa_conv_fprop(const float* x, const float* w, float* out, float* slab, int N, int H, int W, int C, int Kout,
                    int R, int S, int stride, int pad, int splits, int tile, int dgrad, int reduce, int posmajor,
                    hipStream_t st) {
@@ -553,7 +545,6 @@ int dpa_conv_fprop(const float* x, const float* w, float* out, float* slab, int 
   return rc;
 }
 
-// dW[Kout][R*S*C] = sum_m dZ[m][kout] * Xcol[m][rsc]
 int dpa_conv_wgrad(const float* x, const float* dz, float* dw, float* slab, int N, int H, int W, int C, int Kout,
                    int R, int S, int stride, int pad, int splits, int tile, int posmajor, hipStream_t st) {
   ConvArgs a{};

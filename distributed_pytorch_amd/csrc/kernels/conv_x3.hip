@@ -25,13 +25,12 @@
 // MFMA fragments are fetched with the gfx950 transpose read ds_read_b64_tr_b16.
 // Tiles: T128 = 128x128 block, 2x2 waves of 64x64 (2x2 32x32 sub-tiles); T64 = 64x64 block, 1x2
 // waves of 64x32.  Each thread stages one 16-byte chunk per plane per operand per k step.
+#include "api.h"
 #include "common.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
-
-extern "C" int dpa_add_inplace(void* out, const void* add, long n, int bf, hipStream_t s);  // sgd.hip
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -2215,23 +2214,13 @@ int run_pos(PArgs& a, int tile, int splits, int np, int obf, float* slab, void* 
 
 }  // namespace
 
-extern "C" {
-
+extern "C" {  // arguments: api.h
 int dpa_x3_splits(int Kred, int splits) { return xsplits(Kred, splits); }
 
-// rows per row tile of fprop tile `tile` (the stats partial row block), 0 if it cannot emit stats
 int dpa_conv_stats_rows(int tile) {
   return is_pos(tile) ? 0 : (is_stream(tile) ? 256 : (is_halo(tile) ? halo_bm(tile) : tile_rows(tile)));
 }
 
-// x planes [NP][N,H,W,C] (plane stride xps), w planes [NP][Kout][R][S][C] (stride wps; for a data
-// gradient pass the flipped/transposed Wd planes), out fp32 [N,P,Q,Kout] (or slabs, see
-// conv_gemm.hip).  np: 1 (bf16), 3 (fp32 via bf16x6) or 2 (fp32 via fp16 pairs; outputs times
-// h2_out_scale(oscale, obound)).  tile: 0 = 128x128, 1 = 64x64.
-// posmajor: bit 0 = position-major GEMM rows, bit 1 = column-tile-outer block order (Args.nmajor;
-// implicit-GEMM tiles only, the halo kernels ignore it).
-// stats (optional, one split, implicit-GEMM or halo tiles): float2 [Kout][row tiles of conv_stats_rows]
-// BN (mean, M2) partials of the output, channel-major (epi_col_stats), for dpa_bn_finalize_cm.
 int dpa_conv_x3_fprop(const u16* x, long xps, const u16* w, long wps, void* out, float* slab, int N, int H, int W,
                       int C, int Kout, int R, int S, int stride, int pad, int splits, int tile, int reduce,
                       int posmajor, int np, int obf, hipStream_t st, float* stats, float oscale,
@@ -2308,13 +2297,6 @@ int dpa_conv_x3_fprop(const u16* x, long xps, const u16* w, long wps, void* out,
   return 0;
 }
 
-// Data gradient of conv(x [N,H,W,C], w [K,R,S,C], stride, pad) -> dZ [N,Hd,Wd,K]:
-// dx [N,H,W,C] fp32 (or slabs) from dz planes [NP][N,Hd,Wd,K] and the forward weight planes.
-// stride must be a power of two.
-// add (optional, dx's type): dx = dgrad + add -- a second gradient contribution to the same tensor.
-// With split-K it is folded into the reduction (no extra pass); with one split an in-place add
-// follows (an epilogue read of the addend made the bf16 dgrad kernels ~1.7x slower: the loads sit
-// in front of the stores).
 int dpa_conv_x3_dgrad(const u16* dz, long dzps, const u16* w, long wps, void* dx, float* slab, int N, int Hd, int Wd,
                       int K, int C, int R, int S, int stride, int pad, int H, int W, int splits, int tile, int reduce,
                       int posmajor, int np, int obf, hipStream_t st, const void* add, int* sig, int sig_val,
@@ -2438,7 +2420,6 @@ int dpa_conv_x3_dgrad(const u16* dz, long dzps, const u16* w, long wps, void* dx
   return 0;
 }
 
-// dW[Kout][R*S*C] = sum_m dZ[m][kout] Xcol[m][rsc]; x planes [NP][N,H,W,C], dz planes [NP][N,P,Q,Kout]
 int dpa_conv_x3_wgrad(const u16* x, long xps, const u16* dz, long dzps, float* dw, float* slab, int N, int H, int W,
                       int C, int Kout, int R, int S, int stride, int pad, int splits, int tile, int posmajor, int np,
                       hipStream_t st, float oscale, const unsigned* obound) {
@@ -2488,7 +2469,6 @@ int dpa_conv_x3_wgrad(const u16* x, long xps, const u16* dz, long dzps, float* d
   return 0;
 }
 
-// np 2: the fp16 pairs of x * scale (scale a power of two; conv outputs divide it out)
 int dpa_split_planes(const float* x, u16* out, long n, long ps, int np, float scale, hipStream_t st) {
   if (n % 4) return -2;
   if (np == 3)
@@ -2500,7 +2480,6 @@ int dpa_split_planes(const float* x, u16* out, long n, long ps, int np, float sc
   return (int)hipGetLastError();
 }
 
-// np 2: activation planes (scale H2_SA)
 int dpa_pad_split8(const float* x, u16* out, long npix, int cin, long ps, int np, hipStream_t st) {
   if (cin > 8) return -2;
   if (np == 3)

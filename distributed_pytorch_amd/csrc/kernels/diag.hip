@@ -1,4 +1,5 @@
 // Diagnostic kernels (tests and tools only; nothing on the training path).
+#include "api.h"
 #include "common.h"
 
 // One wave sleeps until `ticks` of the constant-rate wall clock have passed, then writes done[0]=1.

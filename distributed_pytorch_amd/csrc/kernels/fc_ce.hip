@@ -4,16 +4,16 @@
 //
 // fc_ce_rows: one wavefront per sample row: logits (wave reductions over Cin), log-sum-exp,
 //   per-row loss, dlogits = (softmax - onehot)/B, and dx = dlogits @ W  — all in registers.
-//   With label smoothing eps (0 <= eps < 1; the SMOOTH training instances, torch's
-//   F.cross_entropy(label_smoothing=eps) with mean reduction and class-index targets):
-//     loss_row  = lse(z) - (1 - eps) * z_t - (eps / J) * sum_j z_j
-//     dlogits_j = (softmax_j - (1 - eps) * [j == t] - eps / J) / B
-//   With pair targets (the MIX training instances: Mixup / CutMix, a second class index and a
-//   per-row lambda) the one-hot target becomes lam * onehot(t1) + (1 - lam) * onehot(t2), see MixArgs.
-//   Evaluation (fc_ce_eval) is always the plain cross-entropy.
+//   The target is a plain class index, a label-smoothed one or a Mixup / CutMix pair (training only;
+//   the formulas and the instance each runs are in ce_target.h).  Evaluation (fc_ce_eval) is always
+//   the plain cross-entropy.
 // fc_ce_wgrad: dW[j][c] = sum_b dlogits[b][j] * x[b][c], db[j] = sum_b dlogits[b][j], and the
 //   batch-mean loss (fixed summation order -> bitwise reproducible).
+#include "api.h"
+#include "ce_target.h"
 #include "common.h"
+
+#include <type_traits>
 
 namespace {
 // Compile-time bounds: MAXJ classes, MAXCL = Cin / 64 values per lane kept in registers.  The VGG
@@ -35,43 +35,16 @@ struct BnIn {
   const float* shift;
 };
 
-// Label smoothing: eps is a trailing kernel argument of the SMOOTH instances only (the pack is empty
-// otherwise), so the plain instances keep the argument list and the code they had before SMOOTH.
-__device__ __forceinline__ float eps_of(float e) { return e; }
-
-// Mixup / CutMix pair targets: the MIX training instances are the ones whose trailing pack is one
-// MixArgs (SMOOTH false; eps rides inside and may be 0), so the plain and the SMOOTH instances keep
-// their names, argument lists and code.  lam is read per row from device memory: a captured graph
-// never bakes it in.  q = lam * onehot(target) + (1 - lam) * onehot(target2):
-//   loss_row  = lse(z) - (1 - eps) * (lam * z_t1 + (1 - lam) * z_t2) - (eps / J) * sum_j z_j
-//   dlogits_j = (softmax_j - (1 - eps) * (lam * [j == t1] + (1 - lam) * [j == t2]) - eps / J) / B
-struct MixArgs {
-  const long long* target2;
-  const float* lam;
-  float eps;
-};
-template <typename... T>
-struct IsMix {
-  static constexpr bool value = false;
-};
-template <>
-struct IsMix<MixArgs> {
-  static constexpr bool value = true;
-};
-__device__ __forceinline__ MixArgs mix_of(MixArgs m) { return m; }
-
-template <bool TRAIN, int MAXJ, int MAXCL, bool BNIN = false, bool SMOOTH = false, typename... Eps>
+template <bool TRAIN, int MAXJ, int MAXCL, bool BNIN, CeMode MODE>
 __global__ __launch_bounds__(256) void fc_ce_rows_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ bias,
                                                          const long long* __restrict__ target,
                                                          float* __restrict__ loss_row, float* __restrict__ dlogits,
                                                          float* __restrict__ dx, int* __restrict__ correct_row,
                                                          float* __restrict__ logits_out, int B, int Cin, int J,
-                                                         BnIn bn = BnIn{nullptr, nullptr, nullptr},
-                                                         Eps... eps_arg) {
-  constexpr bool MIX = IsMix<Eps...>::value;
-  static_assert(sizeof...(Eps) == ((SMOOTH || MIX) ? 1 : 0) && (!(SMOOTH || MIX) || TRAIN) && !(SMOOTH && MIX),
-                "eps: SMOOTH training instances only; MixArgs: MIX training instances only");
+                                                         BnIn bn, CeArgs<MODE> ce) {
+  using Row = CeRow<MODE, int>;
+  static_assert(MODE == CeMode::PLAIN || TRAIN, "SMOOTH and MIX: training instances only");
   extern __shared__ float w_s[];  // [J][Cin]
   // All of the block's W loads are issued together, then the row's loads, and only then is the LDS
   // image written: one memory latency for both instead of one per 4 KB of W plus one for the row
@@ -150,37 +123,24 @@ __global__ __launch_bounds__(256) void fc_ce_rows_kernel(const float* __restrict
   for (int j = 0; j < MAXJ; ++j)
     if (j < J) se += expf(logit[j] - mx);
   const float lse = mx + logf(se);
-  const int t = (int)target[row];
-  float lt = 0.f;
+  const Row tr(ce, target, row);
+  float lt = 0.f, lt2 = 0.f, sz = 0.f;  // the wave holds all J logits: sz in ascending j (fixed order)
 #pragma unroll
   for (int j = 0; j < MAXJ; ++j)
-    if (j == t) lt = logit[j];
-  float lr = lse - lt;
-  if constexpr (SMOOTH) {  // the wave holds all J logits: summed in ascending j (fixed order)
-    const float eps = eps_of(eps_arg...);
-    float sz = 0.f;
+    if (j == tr.t) lt = logit[j];
 #pragma unroll
-    for (int j = 0; j < MAXJ; ++j)
+  for (int j = 0; j < MAXJ; ++j) {
+    if constexpr (Row::SECOND)
+      if (j == tr.t2) lt2 = logit[j];
+    if constexpr (Row::SUM_Z)
       if (j < J) sz += logit[j];
-    lr = lse - (1.f - eps) * lt - eps / (float)J * sz;
   }
-  int t2 = 0;
-  float lam = 1.f;
-  if constexpr (MIX) {
-    const MixArgs m = mix_of(eps_arg...);
-    t2 = (int)m.target2[row];
-    lam = m.lam[row];
-    float lt2 = 0.f, sz = 0.f;
-#pragma unroll
-    for (int j = 0; j < MAXJ; ++j) {
-      if (j == t2) lt2 = logit[j];
-      if (j < J) sz += logit[j];  // ascending j (fixed order), as SMOOTH
-    }
-    lr = lse - (1.f - m.eps) * (lam * lt + (1.f - lam) * lt2) - m.eps / (float)J * sz;
-  }
+  // Once, for the loss and every dlogit.  Keep the conversion here, outside the lane-0 branch: where
+  // it stands decides how the compiler contracts the loss into FMAs, and moving it changes the bits.
+  const float Jf = (float)J;
   if (lane == 0) {
-    loss_row[row] = lr;
-    if (correct_row) correct_row[row] = (arg == t) ? 1 : 0;
+    loss_row[row] = tr.loss(lse, lt, lt2, sz, Jf);
+    if (correct_row) correct_row[row] = (arg == tr.t) ? 1 : 0;
   }
   if (logits_out && lane < J) {
 #pragma unroll
@@ -191,17 +151,7 @@ __global__ __launch_bounds__(256) void fc_ce_rows_kernel(const float* __restrict
     const float invB = 1.f / (float)B;
     float dl[MAXJ];
 #pragma unroll
-    for (int j = 0; j < MAXJ; ++j) {
-      if constexpr (SMOOTH) {
-        const float eps = eps_of(eps_arg...);
-        dl[j] = j < J ? (expf(logit[j] - lse) - (j == t ? 1.f - eps : 0.f) - eps / (float)J) * invB : 0.f;
-      } else if constexpr (MIX) {
-        const float eps = mix_of(eps_arg...).eps;
-        const float q = (j == t ? lam : 0.f) + (j == t2 ? 1.f - lam : 0.f);
-        dl[j] = j < J ? (expf(logit[j] - lse) - (1.f - eps) * q - eps / (float)J) * invB : 0.f;
-      } else
-        dl[j] = j < J ? (expf(logit[j] - lse) - (j == t ? 1.f : 0.f)) * invB : 0.f;
-    }
+    for (int j = 0; j < MAXJ; ++j) dl[j] = j < J ? tr.dlogit(expf(logit[j] - lse), j, Jf, invB) : 0.f;
     if (lane < J) {
 #pragma unroll
       for (int j = 0; j < MAXJ; ++j)
@@ -329,63 +279,49 @@ __global__ __launch_bounds__(256) void eval_accum_kernel(const float* __restrict
   }
 }
 
+// The row kernel's geometry: the BN-in VGG instance, the VGG head's <10, 8>, or the generic one.
+template <bool TRAIN, CeMode MODE>
+void launch_rows(const float* x, const float* w, const float* b, const long long* target, float* loss_row,
+                 float* dlogits, float* dx, int* correct_row, float* logits, int B, int Cin, int J, BnIn bn,
+                 CeArgs<MODE> ce, hipStream_t st) {
+  const int grid = cdiv(B, 4), lds = J * Cin * 4;
+  auto rows = [&](auto mj, auto mcl, auto bnin) {
+    fc_ce_rows_kernel<TRAIN, decltype(mj)::value, decltype(mcl)::value, decltype(bnin)::value, MODE>
+        <<<grid, 256, lds, st>>>(x, w, b, target, loss_row, dlogits, dx, correct_row, logits, B, Cin, J, bn, ce);
+  };
+  using J10 = std::integral_constant<int, 10>;
+  using CL8 = std::integral_constant<int, 8>;
+  if constexpr (TRAIN) {
+    if (bn.z) {
+      rows(J10{}, CL8{}, std::true_type{});
+      return;
+    }
+  }
+  if (J <= 10 && Cin <= 512) {
+    rows(J10{}, CL8{}, std::false_type{});
+  } else {
+    rows(std::integral_constant<int, GEN_J>{}, std::integral_constant<int, GEN_CL>{}, std::false_type{});
+  }
+}
+
 }  // namespace
 
 extern "C" {
 
-// bn_z / bn_scale / bn_shift (optional, VGG head): x is then OUTPUT -- the features are computed from
-// the last conv layer's z [B][2][2][Cin] (BN + ReLU + 2x2 max-pool, see BnIn) and stored there.
-// parts: bit 0 = the row kernel (loss rows, dlogits, dx), bit 1 = the weight-gradient kernel (dW, db,
-// batch loss).  The VGG engine issues the row kernel on the critical path and the weight gradient on
-// its weight-gradient stream (nothing on the critical path reads dW, db or the loss).
-// label_smoothing (0 <= eps < 1, checked by the caller): eps != 0 runs the SMOOTH row kernels, eps == 0
-// the plain ones; only the row kernel sees it (the weight gradient reads dlogits and loss_row).
-// target2 [B] / lam [B] (both or neither; Mixup / CutMix pair targets, see MixArgs): the MIX row kernels,
-// which take eps themselves (0 included); with both null the dispatch is the one above.
+// arguments: api.h
 int dpa_fc_ce_train(const float* x, const float* w, const float* b, const long long* target, float* loss_row,
                     float* dlogits, float* dx, float* dw, float* db, float* loss_out, float* loss_accum, int B,
                     int Cin, int J, hipStream_t st, const float* bn_z, const float* bn_scale, const float* bn_shift,
                     int parts, float label_smoothing, const long long* target2, const float* lam) {
   if (J > GEN_J || Cin > 64 * GEN_CL || Cin % 4 || (long)B * J * 4 > 48 * 1024) return -2;
-  if (!target2 != !lam) return -2;
   const bool rows = parts & 1, wg = parts & 2;
-  const float eps = label_smoothing;
   if (bn_z && (!bn_scale || !bn_shift || J > 10 || Cin > 512)) return -2;
-  if (rows && target2) {
-    const BnIn bn{bn_z, bn_scale, bn_shift};
-    const MixArgs mix{target2, lam, eps};
-    if (bn_z)
-      fc_ce_rows_kernel<true, 10, 8, true, false><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
-          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, bn, mix);
-    else if (J <= 10 && Cin <= 512)
-      fc_ce_rows_kernel<true, 10, 8, false, false><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
-          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, bn, mix);
-    else
-      fc_ce_rows_kernel<true, GEN_J, GEN_CL, false, false><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
-          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, bn, mix);
-  } else if (rows && eps != 0.f) {
-    const BnIn bn{bn_z, bn_scale, bn_shift};
-    if (bn_z)
-      fc_ce_rows_kernel<true, 10, 8, true, true><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
-          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, bn, eps);
-    else if (J <= 10 && Cin <= 512)
-      fc_ce_rows_kernel<true, 10, 8, false, true><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
-          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, bn, eps);
-    else
-      fc_ce_rows_kernel<true, GEN_J, GEN_CL, false, true><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
-          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, bn, eps);
-  } else if (bn_z) {
+  const int bad = ce_dispatch(label_smoothing, target2, lam, [&](auto ce) {
     if (rows)
-      fc_ce_rows_kernel<true, 10, 8, true><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(
-          x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J, BnIn{bn_z, bn_scale, bn_shift});
-  } else if (J <= 10 && Cin <= 512) {
-    if (rows)
-      fc_ce_rows_kernel<true, 10, 8><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(x, w, b, target, loss_row, dlogits, dx,
-                                                                            nullptr, nullptr, B, Cin, J);
-  } else if (rows) {
-    fc_ce_rows_kernel<true, GEN_J, GEN_CL><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(x, w, b, target, loss_row, dlogits,
-                                                                                dx, nullptr, nullptr, B, Cin, J);
-  }
+      launch_rows<true>(x, w, b, target, loss_row, dlogits, dx, nullptr, nullptr, B, Cin, J,
+                        BnIn{bn_z, bn_scale, bn_shift}, ce, st);
+  });
+  if (bad) return bad;
   if (wg) {
     if (J <= 10)
       fc_ce_wgrad_kernel<10><<<cdiv(Cin, 8) + 1, 256, B * J * 4, st>>>(x, dlogits, loss_row, dw, db, loss_out,
@@ -400,13 +336,8 @@ int dpa_fc_ce_train(const float* x, const float* w, const float* b, const long l
 int dpa_fc_ce_eval(const float* x, const float* w, const float* b, const long long* target, float* loss_row,
                    int* correct_row, float* logits, float* acc, int B, int Cin, int J, hipStream_t st) {
   if (J > GEN_J || Cin > 64 * GEN_CL || Cin % 4) return -2;
-  if (J <= 10 && Cin <= 512)
-    fc_ce_rows_kernel<false, 10, 8><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(x, w, b, target, loss_row, nullptr, nullptr,
-                                                                           correct_row, logits, B, Cin, J);
-  else
-    fc_ce_rows_kernel<false, GEN_J, GEN_CL><<<cdiv(B, 4), 256, J * Cin * 4, st>>>(x, w, b, target, loss_row, nullptr,
-                                                                                 nullptr, correct_row, logits, B,
-                                                                                 Cin, J);
+  launch_rows<false>(x, w, b, target, loss_row, nullptr, nullptr, correct_row, logits, B, Cin, J,
+                     BnIn{nullptr, nullptr, nullptr}, CeArgs<CeMode::PLAIN>{}, st);
   if (acc) eval_accum_kernel<<<1, 256, 0, st>>>(loss_row, correct_row, acc, B);
   return (int)hipGetLastError();
 }

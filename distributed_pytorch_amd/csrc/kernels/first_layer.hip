@@ -12,6 +12,7 @@
 // Geometry: x [N,32,32,4] fp32 (4th channel zero), w [64,3,3,CP] KRSC (CP >= 3 padded input
 // channels), z [N,32,32,64].  Block = C0_ROWS image rows of one image (256 pixels); 256 threads =
 // 16 channel quads (fastest, so one pixel's 64 channels are one 256-B store) x 16 pixel lanes.
+#include "api.h"
 #include "common.h"
 
 namespace {
@@ -152,15 +153,9 @@ __global__ __launch_bounds__(256) __attribute__((target("no-packed-fp32-ops"))) 
 
 }  // namespace
 
-extern "C" {
-int dpa_bn_finalize(const float* part, int nblk, int rpb, int M, int C, const float* gamma, const float* beta,
-                    const float* bias, float* rmean, float* rvar, long long* nbt, float* mean, float* invstd,
-                    float* scale, float* shift, float momentum, float eps, hipStream_t st);
-
+extern "C" {  // arguments: api.h
 long dpa_conv0_part_floats(int N) { return 2L * N * (C0_H / C0_ROWS) * C0_C; }
 
-// Training (part != nullptr): conv + per-block statistics, then the BN finalize (batch statistics,
-// running-stat update, scale/shift).  Eval (part == nullptr): conv only.
 int dpa_conv0_fwd(const float* x, const float* w, int CP, float* z, float* part, int N, const float* gamma,
                   const float* beta, const float* bias, float* rmean, float* rvar, long long* nbt, float* mean,
                   float* invstd, float* scale, float* shift, float momentum, float eps, hipStream_t st) {

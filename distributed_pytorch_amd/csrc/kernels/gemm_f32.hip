@@ -12,6 +12,7 @@
 // product), so results match an fp32 dot product in that order.  Split-K over blockIdx.y writes
 // fp32 slabs that common.h's fixed-order split-K reduction sums (deterministic); the bias is added
 // by split 0 only.
+#include "api.h"
 #include "common.h"
 
 namespace {
@@ -91,9 +92,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 
 }  // namespace
 
-extern "C" {
-// C = opA @ opB (+ bias): ak / bk as in the header; splits > 1 needs slab >= splits * M * N floats
-// and M * N % 4 == 0.
+extern "C" {  // arguments: api.h
 int dpa_gemm_f32(const float* A, int lda, int ak, const float* B, int ldb, int bk, float* C, int M, int N, int K,
                  const float* bias, float* slab, int splits, hipStream_t st) {
   if (M <= 0 || N <= 0 || K <= 0) return -2;

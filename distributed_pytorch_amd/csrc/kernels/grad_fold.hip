@@ -10,8 +10,8 @@
 // the accumulated gradient is bitwise the torch.add chain of the micro-steps' gradients.  The shape
 // is sgd_flat_kernel's (sgd.hip): one float4 per thread and iteration, 256 threads, grid-stride
 // under the same block cap; 8 B (store) or 12 B (add, merge) of traffic per element.
+#include "api.h"
 #include "common.h"
-#include "optim_api.h"
 
 template <int MODE>
 __global__ __launch_bounds__(256) void grad_fold_kernel(float* acc, float* g, long n4) {

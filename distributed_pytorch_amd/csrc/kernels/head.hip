@@ -5,17 +5,15 @@
 //
 //   gap        feat[n][c] = mean_hw x[n][hw][c]            (x bf16 or fp32 NHWC, feat fp32)
 //   ce_rows    per row: log-sum-exp, loss_row, dlogits = (softmax - onehot(target)) / N
-//              with label smoothing eps (0 <= eps < 1, torch's F.cross_entropy(label_smoothing=eps)):
-//                loss_row  = lse(z) - (1 - eps) * z_t - (eps / J) * sum_j z_j
-//                dlogits_j = (softmax_j - (1 - eps) * [j == t] - eps / J) / N
-//              with pair targets (Mixup / CutMix: target2 and a per-row lam, the MIX instance) the one-hot
-//              becomes lam * onehot(t) + (1 - lam) * onehot(t2), see MixArgs
-//              (training only: evaluation calls it with eps = 0, the plain cross-entropy)
+//              or its label-smoothed / Mixup-CutMix pair-target form (ce_target.h; training only:
+//              evaluation calls it with eps = 0 and no pair, the plain cross-entropy)
 //   ce_finish  loss = sum_n loss_row[n]  (fixed order)     ; optional running accumulator
 //   bwd_prep   dl = dlogits * dloss ; db[j] = sum_n dl[n][j]   (fixed order)
 //   gap_bwd    dx[n][hw][c] = dfeat[n][c] / HW               (x's dtype)
 //
 // Every reduction has a fixed order: results are bitwise reproducible.
+#include "api.h"
+#include "ce_target.h"
 #include "common.h"
 
 namespace {
@@ -63,43 +61,18 @@ __global__ __launch_bounds__(256) void gap_kernel(const T* __restrict__ x, float
   reinterpret_cast<float4*>(feat)[i] = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
 }
 
-// Label smoothing: eps is a trailing kernel argument of the SMOOTH instance only (the pack is empty
-// otherwise), so the plain instance keeps the argument list and the code it had before SMOOTH.
-__device__ __forceinline__ float eps_of(float e) { return e; }
-
-// Mixup / CutMix pair targets (as fc_ce.hip): the MIX instance is the one whose trailing pack is one
-// MixArgs (SMOOTH false; eps rides inside and may be 0); lam is read per row from device memory.
-//   loss_row  = lse(z) - (1 - eps) * (lam * z_t1 + (1 - lam) * z_t2) - (eps / J) * sum_j z_j
-//   dlogits_j = (softmax_j - (1 - eps) * (lam * [j == t1] + (1 - lam) * [j == t2]) - eps / J) / N
-struct MixArgs {
-  const long long* target2;
-  const float* lam;
-  float eps;
-};
-template <typename... T>
-struct IsMix {
-  static constexpr bool value = false;
-};
-template <>
-struct IsMix<MixArgs> {
-  static constexpr bool value = true;
-};
-__device__ __forceinline__ MixArgs mix_of(MixArgs m) { return m; }
-
 // one 256-thread block per row; J up to any size (strided), block reductions in LDS (fixed order).
-// SMOOTH / MIX: sum_j z_j rides in the sum-of-exp pass and its block reduction (a second LDS array).
-template <bool SMOOTH, typename... Eps>
+// sum_j z_j (the modes that need it) rides in the sum-of-exp pass and its block reduction (a second
+// LDS array).
+template <CeMode MODE>
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits,
                                                       const long long* __restrict__ target,
                                                       float* __restrict__ loss_row, float* __restrict__ dlogits,
-                                                      int* __restrict__ correct_row, int N, int J,
-                                                      Eps... eps_arg) {
-  constexpr bool MIX = IsMix<Eps...>::value;
-  static_assert(sizeof...(Eps) == ((SMOOTH || MIX) ? 1 : 0) && !(SMOOTH && MIX),
-                "eps: the SMOOTH instance only; MixArgs: the MIX instance only");
+                                                      int* __restrict__ correct_row, int N, int J, CeArgs<MODE> ce) {
+  using Row = CeRow<MODE, long long>;
   __shared__ float red[256];
   __shared__ int redi[256];
-  __shared__ float redz[(SMOOTH || MIX) ? 256 : 1];
+  __shared__ float redz[Row::SUM_Z ? 256 : 1];
   const int n = blockIdx.x, t = threadIdx.x;
   const float* lr = logits + (long)n * J;
   float mx = -INFINITY;
@@ -128,61 +101,37 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
   const float m = red[0];
   const int amax = redi[0];
   __syncthreads();
-  float se = 0.f;
-  if constexpr (SMOOTH || MIX) {
-    float sz = 0.f;
-    for (int j = t; j < J; j += 256) {
-      const float v = lr[j];
-      se += __expf(v - m);
-      sz += v;
-    }
-    redz[t] = sz;
-  } else {
-    for (int j = t; j < J; j += 256) se += __expf(lr[j] - m);
+  float se = 0.f, sz = 0.f;
+  for (int j = t; j < J; j += 256) {
+    const float v = lr[j];
+    se += __expf(v - m);
+    if constexpr (Row::SUM_Z) sz += v;
   }
+  if constexpr (Row::SUM_Z) redz[t] = sz;
   red[t] = se;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
     if (t < o) {
       red[t] += red[t + o];
-      if constexpr (SMOOTH || MIX) redz[t] += redz[t + o];
+      if constexpr (Row::SUM_Z) redz[t] += redz[t + o];
     }
     __syncthreads();
   }
   const float sum = red[0];
-  const long long tg = target[n];
+  const Row tr(ce, target, n);
   const float lse = m + __logf(sum);
-  long long tg2 = 0;
-  float lam = 1.f;
-  if constexpr (MIX) {
-    tg2 = mix_of(eps_arg...).target2[n];
-    lam = mix_of(eps_arg...).lam[n];
-  }
   if (t == 0) {
-    if constexpr (SMOOTH) {
-      const float eps = eps_of(eps_arg...);
-      loss_row[n] = lse - (1.f - eps) * lr[tg] - eps / (float)J * redz[0];
-    } else if constexpr (MIX) {
-      const float eps = mix_of(eps_arg...).eps;
-      loss_row[n] = lse - (1.f - eps) * (lam * lr[tg] + (1.f - lam) * lr[tg2]) - eps / (float)J * redz[0];
-    } else
-      loss_row[n] = lse - lr[tg];
-    if (correct_row) correct_row[n] = amax == (int)tg ? 1 : 0;
+    float z_t2 = 0.f;
+    if constexpr (Row::SECOND) z_t2 = lr[tr.t2];
+    // redz[0] is bound by reference: PLAIN never wrote the (one-word) array and its loss() never reads
+    // it.  (float)J stays at the two call sites: hoisting it changes the contraction and the bits.
+    loss_row[n] = tr.loss(lse, lr[tr.t], z_t2, redz[0], (float)J);
+    if (correct_row) correct_row[n] = amax == (int)tr.t ? 1 : 0;
   }
   if (dlogits) {
     const float invN = 1.f / (float)N, inv = 1.f / sum;
-    for (int j = t; j < J; j += 256) {
-      const float p = __expf(lr[j] - m) * inv;
-      if constexpr (SMOOTH) {
-        const float eps = eps_of(eps_arg...);
-        dlogits[(long)n * J + j] = (p - (j == tg ? 1.f - eps : 0.f) - eps / (float)J) * invN;
-      } else if constexpr (MIX) {
-        const float eps = mix_of(eps_arg...).eps;
-        const float q = (j == tg ? lam : 0.f) + (j == tg2 ? 1.f - lam : 0.f);
-        dlogits[(long)n * J + j] = (p - (1.f - eps) * q - eps / (float)J) * invN;
-      } else
-        dlogits[(long)n * J + j] = (p - (j == tg ? 1.f : 0.f)) * invN;
-    }
+    for (int j = t; j < J; j += 256)
+      dlogits[(long)n * J + j] = tr.dlogit(__expf(lr[j] - m) * inv, j, (float)J, invN);
   }
 }
 
@@ -283,16 +232,10 @@ int dpa_gap(const void* x, float* feat, int N, int HW, int C, int xbf, hipStream
 int dpa_ce(const float* logits, const long long* target, float* loss_row, float* dlogits, int* correct_row,
            float* loss, float* acc, int N, int J, hipStream_t st, float label_smoothing, const long long* target2,
            const float* lam) {
-  // label_smoothing (0 <= eps < 1, checked by the caller): eps != 0 runs the SMOOTH row kernel.
-  // target2 [N] / lam [N] (both or neither, else -2): the MIX row kernel, which takes eps itself.
-  if (!target2 != !lam) return -2;
-  if (target2)
-    ce_rows_kernel<false><<<N, 256, 0, st>>>(logits, target, loss_row, dlogits, correct_row, N, J,
-                                             MixArgs{target2, lam, label_smoothing});
-  else if (label_smoothing != 0.f)
-    ce_rows_kernel<true><<<N, 256, 0, st>>>(logits, target, loss_row, dlogits, correct_row, N, J, label_smoothing);
-  else
-    ce_rows_kernel<false><<<N, 256, 0, st>>>(logits, target, loss_row, dlogits, correct_row, N, J);
+  const int bad = ce_dispatch(label_smoothing, target2, lam, [&](auto ce) {
+    ce_rows_kernel<decltype(ce)::MODE><<<N, 256, 0, st>>>(logits, target, loss_row, dlogits, correct_row, N, J, ce);
+  });
+  if (bad) return bad;
   ce_finish_kernel<<<1, 256, 0, st>>>(loss_row, correct_row, N, loss, acc);
   return (int)hipGetLastError();
 }

@@ -31,6 +31,7 @@
 // All ranks issue the same sequence of collectives, so the signal epochs (one per collective,
 // monotonic) agree.  Results are bitwise identical on every rank (each element is reduced once, in
 // rank order 0..W-1, by its slice owner).
+#include "api.h"
 #include "common.h"
 #include "ipc_coll.h"
 

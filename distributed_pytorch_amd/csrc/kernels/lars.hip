@@ -23,8 +23,8 @@
 // Every sum has a fixed order: the element -> thread mapping of (a) depends on the chunk alone,
 // never on the grid, and (b) adds a segment's chunks lane-strided in ascending order and then by
 // a fixed xor-shuffle tree, so the step is bitwise reproducible.
+#include "api.h"
 #include "common.h"
-#include "optim_api.h"
 #include "sgd_update.h"
 
 constexpr int OPT_CHUNK = 8192;

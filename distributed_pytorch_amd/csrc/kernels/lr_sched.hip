@@ -8,8 +8,8 @@
 // lars.hip with the rate source LrWord, sgd_update.h) read *lr once per thread.  Eager steps pass
 // the host's step count (host_pos), so the host count stays the single truth; a captured step is
 // launched with from_device = 1 and advances by itself from replay to replay.
+#include "api.h"
 #include "common.h"
-#include "optim_api.h"
 
 __global__ __launch_bounds__(64) void lr_advance_kernel(const float* __restrict__ table, long T,
                                                         long* __restrict__ step, float* __restrict__ lr,

@@ -9,6 +9,7 @@
 // containing the pixel is visited and its gradient added when the stored position points back at
 // this pixel.  Each input element is written exactly once: no atomics, no zero-fill pass, and the
 // summation order is fixed (deterministic).
+#include "api.h"
 #include "common.h"
 
 namespace {
@@ -232,10 +233,7 @@ int grid_for(long n) {
 
 }  // namespace
 
-extern "C" {
-
-// x [N,H,W,C] (C % 8 == 0) fp32 (bf=0) or bf16 (bf=1) -> y [N,P,Q,C], arg uint8 [N,P,Q,C].
-// scale / shift (both or neither, [C] fp32): x is a BatchNorm input, pooled as relu(x*scale + shift).
+extern "C" {  // arguments: api.h
 int dpa_maxpool_fwd(const void* x, void* y, unsigned char* arg, int N, int H, int W, int C, int k, int s, int p,
                     int bf, hipStream_t st, const float* scale, const float* shift) {
   if (C % 8 || k < 1 || k * k > 255 || s < 1 || p < 0 || p >= k || (scale == nullptr) != (shift == nullptr))
@@ -259,7 +257,6 @@ int dpa_maxpool_fwd(const void* x, void* y, unsigned char* arg, int N, int H, in
   return (int)hipGetLastError();
 }
 
-// dy [N,P,Q,C], arg from the forward -> dx [N,H,W,C] (every element written)
 int dpa_maxpool_bwd(const void* dy, const unsigned char* arg, void* dx, int N, int H, int W, int C, int k, int s,
                     int p, int bf, hipStream_t st) {
   if (C % 8 || k < 1 || k * k > 255 || s < 1 || p < 0 || p >= k) return -2;

@@ -6,8 +6,8 @@
 // torch semantics (dampening 0, nesterov False):
 //   d = g*scale + wd*p ; buf = first ? d : momentum*buf + d ; p -= lr*buf
 // (the per-element code is sgd_update.h, shared with the LARS / clipping update of lars.hip)
+#include "api.h"
 #include "common.h"
-#include "optim_api.h"
 #include "sgd_update.h"
 
 // NP > 0: the updated parameters are also written as NP bf16 operand planes (plane stride ps, same

@@ -13,6 +13,7 @@
 // The poll is bounded: after `ticks` of the 100 MHz wall clock it gives up, sets tmo[0] = 1 and
 // returns, so a missing signal can never hang the device; the engine checks tmo (engine.py
 // check_signals) and raises.
+#include "api.h"
 #include "common.h"
 
 namespace {
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(64) void health_kernel(const int* const* __restrict
 
 }  // namespace
 
-extern "C" {
+extern "C" {  // arguments: api.h
 int dpa_wait_signal(const int* sig, int val, long long timeout_us, int* tmo, hipStream_t st) {
   int dev = 0, khz = 0;
   DPA_HIP_CHECK(hipGetDevice(&dev));
@@ -67,7 +68,6 @@ int dpa_set_signal(int* sig, int val, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-// w: device array of n (<= 63) word pointers; out: 64 ints of host-pinned (device-mapped) memory
 int dpa_health_copy(const int* const* w, int n, int* out, int tag, hipStream_t st) {
   if (n < 0 || n > 63) return -2;
   health_kernel<<<1, 64, 0, st>>>(w, n, out, tag);
