@@ -59,6 +59,15 @@ void need(const Tensor& t, const char* name, at::ScalarType dt = at::kFloat) {
 float* fp(const Tensor& t) { return t.data_ptr<float>(); }
 float* ofp(const OptT& t) { return t.has_value() && t->defined() ? t->data_ptr<float>() : nullptr; }
 
+// the split-K workspace of `op`: nullptr for one split, else the fp32 slab of >= splits * out_elems floats
+float* slab_ptr(const OptT& slab, int64_t splits, int64_t out_elems, const char* op) {
+  if (splits <= 1) return nullptr;
+  TORCH_CHECK(slab.has_value() && slab->defined(), op, ": split-K needs a slab workspace");
+  need(*slab, "slab");
+  TORCH_CHECK(slab->numel() >= splits * out_elems, op, ": slab too small (needs splits * ", out_elems, " floats)");
+  return fp(*slab);
+}
+
 // Mixup / CutMix pair targets of the loss heads: target2 int64 [B] and lam float32 [B], both or neither,
 // on the logits' device.  Returns target2's pointer (null: no mix) and sets *lam_p.
 const long long* mix_targets(const OptT& target2, const OptT& lam, int64_t B, const Tensor& like, const char* what,
@@ -333,14 +342,7 @@ void conv_fprop(Tensor x, Tensor w, Tensor out, OptT slab, int64_t stride, int64
   }
   const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
   TORCH_CHECK(out.size(0) == N && out.size(1) == P && out.size(2) == Q && out.size(3) == K, "conv_fprop: out shape");
-  float* sl = nullptr;
-  const int eff = dpa_conv_splits(R * S * C, (int)splits);
-  if (eff > 1) {
-    TORCH_CHECK(slab.has_value() && slab->defined(), "conv_fprop: split-K needs a slab workspace");
-    need(*slab, "slab");
-    TORCH_CHECK(slab->numel() >= (int64_t)eff * N * P * Q * K, "conv_fprop: slab too small");
-    sl = fp(*slab);
-  }
+  float* sl = slab_ptr(slab, dpa_conv_splits(R * S * C, (int)splits), (int64_t)N * P * Q * K, "conv_fprop");
   chk(dpa_conv_fprop(fp(x), fp(w), fp(out), sl, N, H, W, C, K, R, S, (int)stride, (int)pad, (int)splits, (int)tile,
                      dgrad ? 1 : 0, reduce ? 1 : 0, posmajor ? 1 : 0, cur_stream()),
       "conv_fprop");
@@ -359,14 +361,7 @@ void conv_wgrad(Tensor x, Tensor dz, Tensor dw, OptT slab, int64_t stride, int64
   TORCH_CHECK(dw.size(3) == C && dz.size(3) == K && dz.size(0) == N, "conv_wgrad: shape mismatch");
   const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
   TORCH_CHECK(dz.size(1) == P && dz.size(2) == Q, "conv_wgrad: dz spatial");
-  float* sl = nullptr;
-  const int eff = dpa_conv_splits(N * P * Q, (int)splits);
-  if (eff > 1) {
-    TORCH_CHECK(slab.has_value() && slab->defined(), "conv_wgrad: split-K needs a slab workspace");
-    need(*slab, "slab");
-    TORCH_CHECK(slab->numel() >= (int64_t)eff * K * R * S * C, "conv_wgrad: slab too small");
-    sl = fp(*slab);
-  }
+  float* sl = slab_ptr(slab, dpa_conv_splits(N * P * Q, (int)splits), (int64_t)K * R * S * C, "conv_wgrad");
   chk(dpa_conv_wgrad(fp(x), fp(dz), fp(dw), sl, N, H, W, C, K, R, S, (int)stride, (int)pad, (int)splits, (int)tile,
                      posmajor ? 1 : 0, cur_stream()),
       "conv_wgrad");
@@ -411,6 +406,29 @@ void need_planes(const Tensor& t, const char* name) {
 
 int64_t x3_splits(int64_t Kred, int64_t splits) { return dpa_x3_splits((int)Kred, (int)splits); }
 
+int conv_kind(const std::string& kind) {
+  const int k = kind == "fprop" ? 0 : kind == "dgrad" ? 1 : kind == "wgrad" ? 2 : -1;
+  TORCH_CHECK(k >= 0, "conv kind must be fprop, dgrad or wgrad, got ", kind);
+  return k;
+}
+
+// 0 when `tile` runs call `kind` of conv(x [N,H,W,C], w [K,R,S,C], stride, pad), else the launcher's
+// refusal code (api.h dpa_conv_x3_fits); launches nothing
+int64_t conv_tile_fits(const std::string& kind, int64_t tile, int64_t np, int64_t N, int64_t H, int64_t W, int64_t C,
+                       int64_t K, int64_t R, int64_t S, int64_t stride, int64_t pad, bool obf) {
+  return dpa_conv_x3_fits(conv_kind(kind), (int)tile, (int)np, obf ? 1 : 0, (int)N, (int)H, (int)W, (int)C, (int)K,
+                          (int)R, (int)S, (int)stride, (int)pad);
+}
+
+// [(tile id, family)] of the tiles that run call `kind`, in id order
+std::vector<std::pair<int64_t, std::string>> conv_tile_catalog(const std::string& kind) {
+  static const char* const names[] = {"", "gemm", "halo", "halo_wgrad", "pos", "stream"};
+  std::vector<std::pair<int64_t, std::string>> out;
+  for (int t = 0; t < dpa_conv_x3_tile_end(); ++t)
+    if (const int fam = dpa_conv_x3_tile_family(conv_kind(kind), t)) out.emplace_back(t, names[fam]);
+  return out;
+}
+
 // fp32 conv output, or bf16 (one-plane convs only: the generic bf16-activation path)
 void* conv_out_ptr(const Tensor& out, int np, const char* name, int& obf) {
   TORCH_CHECK(out.is_cuda() && out.is_contiguous(), name, " must be a contiguous GPU tensor");
@@ -440,14 +458,7 @@ void conv_x3_fprop(Tensor x3, Tensor w3, Tensor out, OptT slab, int64_t stride, 
   TORCH_CHECK(w3.size(4) == C, "conv_x3_fprop: channel mismatch");
   const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
   TORCH_CHECK(out.size(0) == N && out.size(1) == P && out.size(2) == Q && out.size(3) == K, "conv_x3_fprop: out shape");
-  float* sl = nullptr;
-  const int eff = dpa_x3_splits(R * S * C, (int)splits);
-  if (eff > 1) {
-    TORCH_CHECK(slab.has_value() && slab->defined(), "conv_x3_fprop: split-K needs a slab workspace");
-    need(*slab, "slab");
-    TORCH_CHECK(slab->numel() >= (int64_t)eff * N * P * Q * K, "conv_x3_fprop: slab too small");
-    sl = fp(*slab);
-  }
+  float* sl = slab_ptr(slab, dpa_x3_splits(R * S * C, (int)splits), (int64_t)N * P * Q * K, "conv_x3_fprop");
   float* stp = nullptr;
   if (stats.has_value() && stats->defined()) {  // BN partials from the epilogue (one split only)
     need(*stats, "stats");
@@ -494,14 +505,7 @@ void conv_x3_wgrad(Tensor x3, Tensor dz3, Tensor dw, OptT slab, int64_t stride, 
   TORCH_CHECK(dw.size(3) == C && dz3.size(4) == K && dz3.size(1) == N, "conv_x3_wgrad: shape mismatch");
   const int P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
   TORCH_CHECK(dz3.size(2) == P && dz3.size(3) == Q, "conv_x3_wgrad: dz spatial");
-  float* sl = nullptr;
-  const int eff = dpa_x3_splits(N * P * Q, (int)splits);
-  if (eff > 1) {
-    TORCH_CHECK(slab.has_value() && slab->defined(), "conv_x3_wgrad: split-K needs a slab workspace");
-    need(*slab, "slab");
-    TORCH_CHECK(slab->numel() >= (int64_t)eff * K * R * S * C, "conv_x3_wgrad: slab too small");
-    sl = fp(*slab);
-  }
+  float* sl = slab_ptr(slab, dpa_x3_splits(N * P * Q, (int)splits), (int64_t)K * R * S * C, "conv_x3_wgrad");
   chk(dpa_conv_x3_wgrad(up(x3), x3.stride(0), up(dz3), dz3.stride(0), fp(dw), sl, N, H, W, C, K, R, S, (int)stride,
                         (int)pad, (int)splits, (int)tile, (int)posmajor, np, cur_stream(), (float)oscale,
                         bound_ptr(obound, "conv_x3_wgrad")),
@@ -526,14 +530,7 @@ void conv_x3_dgrad(Tensor dz3, Tensor w3, Tensor dx, OptT slab, int64_t stride, 
   TORCH_CHECK(dx.size(0) == N && dx.size(3) == C, "conv_x3_dgrad: dx shape");
   TORCH_CHECK((H + 2 * pad - R) / stride + 1 == Hd && (W + 2 * pad - S) / stride + 1 == Wd,
               "conv_x3_dgrad: dz spatial does not match conv(dx)");
-  float* sl = nullptr;
-  const int eff = dpa_x3_splits(R * S * K, (int)splits);
-  if (eff > 1) {
-    TORCH_CHECK(slab.has_value() && slab->defined(), "conv_x3_dgrad: split-K needs a slab workspace");
-    need(*slab, "slab");
-    TORCH_CHECK(slab->numel() >= (int64_t)eff * N * H * W * C, "conv_x3_dgrad: slab too small");
-    sl = fp(*slab);
-  }
+  float* sl = slab_ptr(slab, dpa_x3_splits(R * S * K, (int)splits), (int64_t)N * H * W * C, "conv_x3_dgrad");
   const void* ap = nullptr;
   if (add.has_value() && add->defined()) {
     TORCH_CHECK(add->is_cuda() && add->is_contiguous() && add->numel() == dx.numel() &&
@@ -753,13 +750,7 @@ void gemm_f32(Tensor A, Tensor B, Tensor C, bool trans_a, bool trans_b, OptT bia
   const int M = trans_a ? A.size(1) : A.size(0), K = trans_a ? A.size(0) : A.size(1);
   const int N = trans_b ? B.size(0) : B.size(1), KB = trans_b ? B.size(1) : B.size(0);
   TORCH_CHECK(K == KB && C.size(0) == M && C.size(1) == N, "gemm_f32: shapes");
-  float* sp = nullptr;
-  if (splits > 1) {
-    TORCH_CHECK(slab.has_value() && slab->defined() && slab->numel() >= splits * (int64_t)M * N,
-                "gemm_f32: split-K needs a slab of splits * M * N floats");
-    need(*slab, "slab");
-    sp = fp(*slab);
-  }
+  float* sp = slab_ptr(slab, splits, (int64_t)M * N, "gemm_f32");
   if (bias.has_value() && bias->defined()) TORCH_CHECK(bias->numel() == N, "gemm_f32: bias [N]");
   chk(dpa_gemm_f32(fp(A), A.size(1), trans_a ? 0 : 1, fp(B), B.size(1), trans_b ? 1 : 0, fp(C), M, N, K, ofp(bias), sp,
                    (int)splits, cur_stream()),
@@ -1319,6 +1310,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("pad"), py::arg("splits") = 1, py::arg("tile") = 0, py::arg("posmajor") = false);
   m.def("wflip", &wflip);
   m.def("x3_splits", &x3_splits);
+  m.def("conv_tile_fits", &conv_tile_fits, py::arg("kind"), py::arg("tile"), py::arg("np"), py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("C"), py::arg("K"), py::arg("R"), py::arg("S"), py::arg("stride"), py::arg("pad"),
+        py::arg("obf") = false);
+  m.def("conv_tile_catalog", &conv_tile_catalog, py::arg("kind"));
   m.def("conv_x3_fprop", &conv_x3_fprop, py::arg("x3"), py::arg("w3"), py::arg("out"), py::arg("slab"),
         py::arg("stride"), py::arg("pad"), py::arg("splits") = 1, py::arg("tile") = 0, py::arg("reduce") = true,
         py::arg("posmajor") = 0, py::arg("stats") = py::none(), py::arg("oscale") = 1.0,

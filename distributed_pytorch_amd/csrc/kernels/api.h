@@ -123,6 +123,17 @@ int dpa_wflip(const float* w, float* wd, int K, int R, int S, int C, hipStream_t
 int dpa_x3_splits(int Kred, int splits);
 // rows per row tile of fprop tile `tile` (the stats partial row block), 0 if it cannot emit stats
 int dpa_conv_stats_rows(int tile);
+// The tile catalog (conv_x3.hip TILES).  kind: 0 fprop, 1 dgrad, 2 wgrad.  Tile ids are below
+// dpa_conv_x3_tile_end(); the family of the tile that runs `kind` under id `tile` is 1 implicit GEMM,
+// 2 halo, 3 halo weight gradient, 4 position-major, 5 streaming GEMM, or 0: no such tile.
+int dpa_conv_x3_tile_end();
+int dpa_conv_x3_tile_family(int kind, int tile);
+// Whether `tile` runs call `kind` of conv(x [N,H,W,C], w [K,R,S,C], stride, pad) with np operand
+// planes and fp32 (obf 0) or bf16 (obf 1) output: 0, or the code the launcher below refuses the call
+// with before it launches anything (-2 channels % 8, -3 stride, -4 bf16 output, -5 a plane of 2 GiB,
+// -6 the conv does not fit the tile or the catalog has no such tile).  Host only.
+int dpa_conv_x3_fits(int kind, int tile, int np, int obf, int N, int H, int W, int C, int K, int R, int S, int stride,
+                     int pad);
 // x planes [NP][N,H,W,C] (plane stride xps), w planes [NP][Kout][R][S][C] (stride wps; for a data
 // gradient pass the flipped/transposed Wd planes), out fp32 [N,P,Q,Kout] (or slabs, see
 // dpa_conv_fprop).  np: 1 (bf16), 3 (fp32 via bf16x6) or 2 (fp32 via fp16 pairs; outputs times

@@ -1879,6 +1879,215 @@ __global__ __launch_bounds__(256) void pad_split_kernel(const float* __restrict_
   }
 }
 
+// ---- the tile catalog: every tile id, its family and that family's template parameters.  Dispatch
+// (with_tile), admission (tile_fits), dpa_conv_stats_rows and the exported catalog query read it.
+//   F_GEMM        conv_x3_kernel: any conv, all three kinds.  ns 1: single LDS stage, 2: double-
+//                 buffered, 3 / 4: those with two register tiles in flight
+//   F_HALO        conv_halo_kernel: 3x3 / stride 1 / pad 1 fprop and dgrad.  20, 21, 23: 64-column
+//                 tiles for 64-channel outputs (e.g. the data gradient into a 64-channel layer);
+//                 22, 23: 64-channel chunks, four k-steps of MFMAs per barrier instead of two
+//   F_HALO_WGRAD  conv_halo_wgrad_kernel: the weight gradient of those convs (ids 16, 17 again)
+//   F_POS         conv_pos_kernel: F_HALO's convs on small images (2x2: ni 64, 4x4: ni 32)
+//   F_STREAM      gemm_stream_kernel: 1x1 / stride 1 / pad 0 fprop and dgrad, bf16 in and out, one split
+enum Family { F_GEMM = 1, F_HALO, F_HALO_WGRAD, F_POS, F_STREAM };
+struct Tile {
+  int id, fam;
+  int bm, bn, wm, wn;  // block tile rows x columns, waves along each (F_HALO_WGRAD: bm = pixels per chunk)
+  int bc;              // F_GEMM: stage depth BK; the others: channels per staged chunk
+  int ns;              // F_GEMM: NSTAGE
+  int ni, nspx, pd;    // F_POS: images per tile, staged pixels it holds, weight tiles in flight
+};
+constexpr Tile TILES[] = {
+    {0, F_GEMM, 128, 128, 2, 2, 32, 2},  {1, F_GEMM, 64, 64, 1, 2, 32, 2},    {2, F_GEMM, 128, 128, 2, 2, 16, 2},
+    {3, F_GEMM, 64, 64, 1, 2, 64, 2},    {4, F_GEMM, 128, 128, 2, 2, 16, 1},  {5, F_GEMM, 128, 128, 2, 2, 32, 1},
+    {6, F_GEMM, 64, 64, 1, 2, 32, 1},    {7, F_GEMM, 256, 128, 4, 2, 32, 1},  {8, F_GEMM, 128, 128, 2, 2, 32, 3},
+    {9, F_GEMM, 128, 128, 2, 2, 16, 3},  {10, F_GEMM, 256, 128, 4, 2, 32, 3}, {11, F_GEMM, 64, 64, 1, 2, 32, 3},
+    {12, F_GEMM, 128, 128, 2, 2, 32, 4}, {13, F_GEMM, 128, 128, 2, 2, 16, 4}, {14, F_GEMM, 256, 128, 4, 2, 32, 4},
+    {15, F_GEMM, 64, 64, 1, 2, 32, 4},
+    {16, F_HALO, 256, 128, 4, 2, 16},    {17, F_HALO, 256, 128, 4, 2, 32},    {18, F_HALO, 128, 128, 2, 2, 16},
+    {19, F_HALO, 128, 128, 2, 2, 32},    {20, F_HALO, 256, 64, 4, 2, 32},     {21, F_HALO, 128, 64, 2, 2, 32},
+    {22, F_HALO, 256, 128, 4, 2, 64},    {23, F_HALO, 256, 64, 4, 2, 64},
+    {16, F_HALO_WGRAD, 64, 128, 4, 1, 32},  // a block: 128 (k) x 32 (c) of all 9 taps
+    {17, F_HALO_WGRAD, 32, 128, 4, 1, 32},
+    {24, F_POS, 256, 128, 4, 2, 32, 0, 32, 12, 1}, {25, F_POS, 256, 128, 4, 2, 32, 0, 32, 12, 4},
+    {26, F_POS, 256, 128, 4, 2, 32, 0, 64, 4, 1},  {27, F_POS, 256, 64, 4, 2, 32, 0, 64, 4, 1},
+    {28, F_POS, 256, 64, 4, 2, 32, 0, 64, 4, 4},   {29, F_POS, 256, 128, 4, 2, 16, 0, 32, 12, 1},
+    {30, F_STREAM, 256, 128, 4, 2, 32},
+};
+constexpr int NTILES = sizeof(TILES) / sizeof(TILES[0]);
+
+// the catalog entry that runs call `kind` (XM_*) under tile id `id`, or nullptr
+const Tile* find_tile(int kind, int id) {
+  for (const Tile& t : TILES)
+    if (t.id == id && (t.fam == F_GEMM || (t.fam == F_HALO_WGRAD) == (kind == XM_WGRAD))) return &t;
+  return nullptr;
+}
+
+// f(integral_constant<int, I>) for the entry TILES[I] of family FAM with this id; f is instantiated
+// for that family's entries only.  -6: the family has no such tile.
+template <int FAM, int I, class F>
+bool try_tile(int id, F& f, int& rc) {
+  if constexpr (TILES[I].fam == FAM) {
+    if (TILES[I].id == id) {
+      rc = f(std::integral_constant<int, I>{});
+      return true;
+    }
+  }
+  return false;
+}
+template <int FAM, class F, int... I>
+int with_tile(int id, F f, std::integer_sequence<int, I...>) {
+  int rc = -6;
+  (void)(try_tile<FAM, I>(id, f, rc) || ...);
+  return rc;
+}
+template <int FAM, class F>
+int with_tile(int id, F f) {
+  return with_tile<FAM>(id, f, std::make_integer_sequence<int, NTILES>{});
+}
+
+// ---- admission: which conv a tile runs ----
+// The forward conv x [N,H,W,C] * w [K,R,S,C] -> [N,P,Q,K] that a call belongs to (a data gradient
+// reads dZ [N,P,Q,K] and writes dX [N,H,W,C]).
+struct Geo {
+  int N, H, W, C, K, R, S, stride, pad, P, Q;
+  long xel(int kind) const { return kind == XM_DGRAD ? (long)N * P * Q * K : (long)N * H * W * C; }  // A planes
+  long wel(int kind) const { return kind == XM_WGRAD ? (long)N * P * Q * K : (long)K * R * S * C; }  // B planes
+  int cred(int kind) const { return kind == XM_DGRAD ? K : C; }  // fprop / dgrad: channels reduced,
+  int cout(int kind) const { return kind == XM_DGRAD ? C : K; }  // channels produced
+};
+
+Geo make_geo(int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
+  Geo g{N, H, W, C, K, R, S, stride, pad, 0, 0};
+  if (stride > 0) {
+    g.P = (H + 2 * pad - R) / stride + 1;
+    g.Q = (W + 2 * pad - S) / stride + 1;
+  }
+  return g;
+}
+
+// three planes of a 64-channel chunk do not fit the LDS
+constexpr bool halo_planes_fit(int bc, int np) { return !(bc >= 64 && np == 3); }
+
+// staged pixels of the worst position block, or -1 when the positions do not tile the image
+int pos_staged(int H, int W, int ppt) {
+  if (H < 2 || W < 2 || (H * W) % ppt) return -1;
+  int worst = 0;
+  for (int p0 = 0; p0 < H * W; p0 += ppt) {
+    const int ylo = std::max(0, p0 / W - 1), yhi = std::min(H, (p0 + ppt - 1) / W + 2);
+    worst = std::max(worst, (yhi - ylo) * W);
+  }
+  return worst;
+}
+
+bool is_3x3s1p1(const Geo& g) {
+  return g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.P == g.H && g.Q == g.W;
+}
+
+// The one rule per family.  0: the tile runs the call.  -2: channels not a multiple of 8; -3: a
+// stride the data gradient cannot take; -6: the conv does not fit the tile (conv shape, channels
+// per chunk, rows wider or more staged pixels than the tile's image holds, plane count, output type).
+int fits_gemm(int kind, const Geo& g) {
+  if (kind == XM_DGRAD && ((g.stride & (g.stride - 1)) || g.R - 1 - g.pad < 0)) return -3;
+  return g.C % 8 || g.K % 8 ? -2 : 0;
+}
+int fits_halo(const Tile& t, int kind, int np, const Geo& g) {
+  if (!is_3x3s1p1(g) || g.cred(kind) % t.bc || g.cout(kind) % 8 || !halo_planes_fit(t.bc, np)) return -6;
+  return t.bm + 2 * g.W + 2 > halo_slots(t.bm, t.bc, np) - 1 ? -6 : 0;
+}
+int fits_halo_wgrad(const Tile& t, const Geo& g) {
+  return !is_3x3s1p1(g) || g.C % 8 || g.K % 8 || t.bm + 2 * g.W + 2 > halo_wslots(t.bm) - 1 ? -6 : 0;
+}
+int fits_pos(const Tile& t, int kind, int obf, const Geo& g) {
+  if (!is_3x3s1p1(g) || obf || g.cred(kind) % t.bc || g.cout(kind) % 8) return -6;
+  const int ns = pos_staged(g.H, g.W, t.bm / t.ni);
+  return ns < 0 || ns > t.nspx ? -6 : 0;
+}
+int fits_stream(int np, int obf, const Geo& g) {
+  return g.R != 1 || g.S != 1 || g.stride != 1 || g.pad != 0 || np != 1 || !obf || g.C % 8 || g.K % 8 ? -6 : 0;
+}
+
+// 0, or why tile `t` (find_tile's answer) refuses the call: the family's rule, then -5: an operand
+// plane of 2 GiB or more (32-bit buffer offsets), then -4: bf16 output from other than one-plane
+// fprop / dgrad operands (unreduced slabs stay fp32).
+int tile_fits(int kind, const Tile* t, int np, int obf, const Geo& g) {
+  if (!t) return -6;
+  if (g.stride < 1) return -3;
+  const int rc = t->fam == F_GEMM         ? fits_gemm(kind, g)
+                 : t->fam == F_HALO       ? fits_halo(*t, kind, np, g)
+                 : t->fam == F_HALO_WGRAD ? fits_halo_wgrad(*t, g)
+                 : t->fam == F_POS        ? fits_pos(*t, kind, obf, g)
+                                          : fits_stream(np, obf, g);
+  if (rc) return rc;
+  if (g.xel(kind) * 2 >= (1L << 31) || g.wel(kind) * 2 >= (1L << 31)) return -5;
+  return obf && (np != 1 || kind == XM_WGRAD) ? -4 : 0;
+}
+
+// ---- launch pieces the families share ----
+// epilogue stores staged through LDS as 16-byte row pieces (conv_x3_kernel / conv_halo_kernel): measured
+// faster than direct 2-/4-byte stores on every conv of the VGG and ResNet steps (docs/PERF_NOTES.md)
+constexpr int ob_epi() { return 1; }
+
+int grid_1d(long n) {
+  long g = (n + 255) / 256;
+  if (g > 4096) g = 4096;
+  return (int)(g < 1 ? 1 : g);
+}
+
+int xsplits(int Kred, int splits) {
+  const int nt = cdiv(Kred, BKMIN);
+  if (splits < 1) splits = 1;
+  if (splits > nt) splits = nt;
+  return splits < 1 ? 1 : splits;
+}
+
+// The operands of one call.  args<A>() starts family A's argument struct from them: the plane
+// pointers, strides and descriptor ranges (bytes of one plane), the output scale, the start signal.
+struct Operands {
+  const u16* x;
+  long xps;
+  const u16* w;
+  long wps;
+  float oscale;
+  const unsigned* obound;
+  int* sig;
+  int sig_val;
+};
+
+template <class A>
+A args(const Operands& o, int kind, const Geo& g) {
+  A a{};
+  a.x = o.x;
+  a.xps = o.xps;
+  a.xbytes = (unsigned)(g.xel(kind) * 2);
+  if constexpr (std::is_same_v<A, WHArgs>) {  // the second operand is dZ; no start signal
+    a.dz = o.w;
+    a.dzps = o.wps;
+    a.dzbytes = (unsigned)(g.wel(kind) * 2);
+  } else {
+    a.w = o.w;
+    a.wps = o.wps;
+    a.wbytes = (unsigned)(g.wel(kind) * 2);
+    a.sig = o.sig;
+    a.sig_val = o.sig_val;
+  }
+  a.oscale = o.oscale;
+  a.obound = o.obound;
+  return a;
+}
+
+// What follows the conv kernel of an n-element output.  One split: out is written, an addend is
+// added in place.  Several: the slabs are reduced into out together with the addend, or left
+// (!reduce; an addend would be lost: -4, asked before the launch).
+bool addend_lost(const void* add, int splits, int reduce) { return add && splits > 1 && !reduce; }
+int finish_splitk(float* slab, void* out, long n, int splits, int reduce, int obf, const void* add, hipStream_t st) {
+  if (splits == 1) return add ? dpa_add_inplace(out, add, n, obf, st) : 0;
+  if (!reduce) return 0;
+  if (obf) return launch_splitk_reduce_t(slab, (ushort4*)out, n / 4, splits, st, (const ushort4*)add);
+  return launch_splitk_reduce_t(slab, (float4*)out, n / 4, splits, st, (const float4*)add);
+}
+
+// ---- implicit-GEMM tiles ----
 template <int BM, int BN, int WM, int WN, int MODE, int NP, int BK, int NS, bool OB>
 int launch_x3(const Args& a, hipStream_t st) {
   dim3 grid(a.gm * a.gn, a.splits, a.nph > 1 ? a.nph : 1);
@@ -1886,53 +2095,22 @@ int launch_x3(const Args& a, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-// tile id -> (block tile, stage depth, LDS stages):
-//   0: 128x128/k32/2  1: 64x64/k32/2  2: 128x128/k16/2  3: 64x64/k64/2
-//   4: 128x128/k16/1  5: 128x128/k32/1  6: 64x64/k32/1  7: 256x128/k32/1 (8 waves)
-//   8-11: the 128x128/k32, 128x128/k16, 256x128/k32, 64x64/k32 single-stage tiles with two register
-//   tiles in flight (NSTAGE 3)
-//   12-15: 128x128/k32, 128x128/k16, 256x128/k32, 64x64/k32 double-buffered with two register
-//   tiles in flight (NSTAGE 4)
 template <int MODE, int NP, bool OB = false>
 int launch_tile(const Args& a, int tile, hipStream_t st) {
-  switch (tile) {
-    case 7: return launch_x3<256, 128, 4, 2, MODE, NP, 32, 1, OB>(a, st);
-    case 8: return launch_x3<128, 128, 2, 2, MODE, NP, 32, 3, OB>(a, st);
-    case 9: return launch_x3<128, 128, 2, 2, MODE, NP, 16, 3, OB>(a, st);
-    case 10: return launch_x3<256, 128, 4, 2, MODE, NP, 32, 3, OB>(a, st);
-    case 11: return launch_x3<64, 64, 1, 2, MODE, NP, 32, 3, OB>(a, st);
-    case 12: return launch_x3<128, 128, 2, 2, MODE, NP, 32, 4, OB>(a, st);
-    case 13: return launch_x3<128, 128, 2, 2, MODE, NP, 16, 4, OB>(a, st);
-    case 14: return launch_x3<256, 128, 4, 2, MODE, NP, 32, 4, OB>(a, st);
-    case 15: return launch_x3<64, 64, 1, 2, MODE, NP, 32, 4, OB>(a, st);
-    case 0: return launch_x3<128, 128, 2, 2, MODE, NP, 32, 2, OB>(a, st);
-    case 1: return launch_x3<64, 64, 1, 2, MODE, NP, 32, 2, OB>(a, st);
-    case 2: return launch_x3<128, 128, 2, 2, MODE, NP, 16, 2, OB>(a, st);
-    case 3: return launch_x3<64, 64, 1, 2, MODE, NP, 64, 2, OB>(a, st);
-    case 4: return launch_x3<128, 128, 2, 2, MODE, NP, 16, 1, OB>(a, st);
-    case 5: return launch_x3<128, 128, 2, 2, MODE, NP, 32, 1, OB>(a, st);
-    default: return launch_x3<64, 64, 1, 2, MODE, NP, 32, 1, OB>(a, st);
-  }
+  return with_tile<F_GEMM>(tile, [&](auto i) {
+    constexpr Tile t = TILES[decltype(i)::value];
+    return launch_x3<t.bm, t.bn, t.wm, t.wn, MODE, NP, t.bc, t.ns, OB>(a, st);
+  });
 }
 
-// fp32 output, or bf16 output (np == 1 only) for the generic bf16-activation path
+// fp32 output, or bf16 output (np == 1 only; fprop and dgrad) for the generic bf16-activation path
 template <int MODE>
 int launch_any(const Args& a, int tile, int np, int obf, hipStream_t st) {
-  if (obf) return launch_tile<MODE, 1, true>(a, tile, st);
+  if constexpr (MODE != XM_WGRAD) {
+    if (obf) return launch_tile<MODE, 1, true>(a, tile, st);
+  }
   if (np == 2) return launch_tile<MODE, 2>(a, tile, st);
   return np == 3 ? launch_tile<MODE, 3>(a, tile, st) : launch_tile<MODE, 1>(a, tile, st);
-}
-// epilogue stores staged through LDS as 16-byte row pieces (conv_x3_kernel / conv_halo_kernel): measured
-// faster than direct 2-/4-byte stores on every conv of the VGG and ResNet steps (docs/PERF_NOTES.md)
-constexpr int ob_epi() { return 1; }
-bool small_tile(int tile) { return tile == 1 || tile == 3 || tile == 6 || tile == 11 || tile == 15; }
-int tile_rows(int tile) { return small_tile(tile) ? 64 : ((tile == 7 || tile == 10 || tile == 14) ? 256 : 128); }
-int tile_cols(int tile) { return small_tile(tile) ? 64 : 128; }
-
-int grid_1d(long n) {
-  long g = (n + 255) / 256;
-  if (g > 4096) g = 4096;
-  return (int)(g < 1 ? 1 : g);
 }
 
 void fill(Args& a, int N, int H, int W, int C, int R, int S, int stride, int pad) {
@@ -1955,34 +2133,25 @@ void fill(Args& a, int N, int H, int W, int C, int R, int S, int stride, int pad
   a.fd_N = make_fastdiv(N);
 }
 
-// descriptor ranges (bytes of one plane); the 32-bit buffer offsets need planes < 2 GiB
-int set_bytes(Args& a, long xelems, long welems) {
-  if (xelems * 2 >= (1L << 31) || welems * 2 >= (1L << 31)) return 1;
-  a.xbytes = (unsigned)(xelems * 2);
-  a.wbytes = (unsigned)(welems * 2);
-  return 0;
+// The launch of a filled Args: a rows x cols GEMM reduced over kred into `n` output elements.
+template <int MODE>
+int run_gemm(Args& a, const Tile& t, int rows, int cols, int kred, long n, int splits, int posmajor, int np, int obf,
+             float* slab, void* out, int reduce, const void* add, hipStream_t st) {
+  a.gm = cdiv(rows, t.bm);
+  a.gn = cdiv(cols, t.bn);
+  a.splits = xsplits(kred, splits);
+  a.posmajor = posmajor & 1;
+  a.nmajor = (posmajor >> 1) & 1;
+  a.sepi = ob_epi();
+  a.out = a.splits > 1 ? slab : (float*)out;
+  a.outb = MODE == XM_WGRAD ? nullptr : (u16*)out;
+  a.slab = a.splits > 1 ? n : 0;
+  if (addend_lost(add, a.splits, reduce)) return -4;
+  const int rc = launch_any<MODE>(a, t.id, np, obf && a.splits == 1, st);
+  return rc ? rc : finish_splitk(slab, out, n, a.splits, reduce, obf, add, st);
 }
 
-int xsplits(int Kred, int splits) {
-  const int nt = cdiv(Kred, BKMIN);
-  if (splits < 1) splits = 1;
-  if (splits > nt) splits = nt;
-  return splits < 1 ? 1 : splits;
-}
-
-// ---- halo tiles: ids 16-21 follow the 16 implicit-GEMM tiles (3x3, stride 1, pad 1 only) ----
-//   FPROP / DGRAD: 16 = 256x128 with 16-channel chunks (8 waves), 17 = 256x128 / 32,
-//                  18 = 128x128 / 16 (4 waves), 19 = 128x128 / 32,
-//                  20 = 256x64 / 32 (8 waves of 64x32), 21 = 128x64 / 32 (4 waves of 64x32) for
-//                  64-channel outputs (e.g. the data gradient into a 64-channel layer),
-//                  22 = 256x128 / 64, 23 = 256x64 / 64 (8 waves; NP 1, or NP 2 with rows <= 16 px):
-//                  four k-steps of MFMAs per barrier instead of two,
-//   WGRAD:         16 = 64-pixel chunks, 17 = 32-pixel chunks
-bool is_halo(int tile) { return tile >= 16 && tile <= 23; }
-int halo_bm(int tile) { return (tile <= 17 || tile == 20 || tile >= 22) ? 256 : 128; }
-int halo_bn(int tile) { return tile == 20 || tile == 21 || tile == 23 ? 64 : 128; }
-int halo_bc(int tile) { return tile >= 22 ? 64 : ((tile & 1) || tile == 20 ? 32 : 16); }
-
+// ---- halo tiles ----
 template <int BM, int BN, int WM, int WN, bool DG, int NP, int BC, bool OB>
 int launch_halo(const HArgs& a, int splits, hipStream_t st) {
   dim3 grid(a.gm * a.gn, splits);
@@ -1992,64 +2161,46 @@ int launch_halo(const HArgs& a, int splits, hipStream_t st) {
 
 template <bool DG, int NP, bool OB>
 int launch_halo_tile(const HArgs& a, int tile, int splits, hipStream_t st) {
-  switch (tile) {
-    case 16: return launch_halo<256, 128, 4, 2, DG, NP, 16, OB>(a, splits, st);
-    case 17: return launch_halo<256, 128, 4, 2, DG, NP, 32, OB>(a, splits, st);
-    case 18: return launch_halo<128, 128, 2, 2, DG, NP, 16, OB>(a, splits, st);
-    case 20: return launch_halo<256, 64, 4, 2, DG, NP, 32, OB>(a, splits, st);
-    case 21: return launch_halo<128, 64, 2, 2, DG, NP, 32, OB>(a, splits, st);
-    case 22:
-    case 23:
-      if constexpr (NP == 3) {  // three planes of a 64-channel chunk do not fit the LDS
-        return -6;
-      } else {
-        return tile == 22 ? launch_halo<256, 128, 4, 2, DG, NP, 64, OB>(a, splits, st)
-                          : launch_halo<256, 64, 4, 2, DG, NP, 64, OB>(a, splits, st);
-      }
-    default: return launch_halo<128, 128, 2, 2, DG, NP, 32, OB>(a, splits, st);
-  }
+  return with_tile<F_HALO>(tile, [&](auto i) {
+    constexpr Tile t = TILES[decltype(i)::value];
+    if constexpr (halo_planes_fit(t.bc, NP))
+      return launch_halo<t.bm, t.bn, t.wm, t.wn, DG, NP, t.bc, OB>(a, splits, st);
+    else
+      return -6;
+  });
 }
 
-// -6: the conv does not fit the halo tile (channels, rows wider than the staged image allows, or
-// three planes of a 64-channel chunk)
 template <bool DG>
-int run_halo(HArgs& a, int tile, int splits, int np, int obf, float* slab, void* out, int reduce, hipStream_t st,
-             const void* add = nullptr) {
-  const int BM = halo_bm(tile), BC = halo_bc(tile);
-  if (a.C % BC || a.Nout % 8 || BM + 2 * a.W + 2 > halo_slots(BM, BC, np) - 1) return -6;
-  if (BC >= 64 && np == 3) return -6;
-  if (obf && np != 1) return -4;  // bf16 output from one-plane operands (unreduced slabs stay fp32)
+int run_halo(const Operands& o, const Geo& g, const Tile& t, int splits, int np, int obf, float* slab, void* out,
+             int reduce, float* stats, const void* add, hipStream_t st) {
+  constexpr int kind = DG ? XM_DGRAD : XM_FPROP;
+  HArgs a = args<HArgs>(o, kind, g);
+  a.N = g.N;
+  a.H = g.H;
+  a.W = g.W;
+  a.C = g.cred(kind);
+  a.Nout = g.cout(kind);
+  a.stats = reinterpret_cast<float2*>(stats);
   a.M = a.N * a.H * a.W;
-  a.gm = cdiv(a.M, BM);
-  a.gn = cdiv(a.Nout, halo_bn(tile));
+  a.gm = cdiv(a.M, t.bm);
+  a.gn = cdiv(a.Nout, t.bn);
   a.sepi = ob_epi();
-  a.cps = cdiv(a.C / BC, splits);
+  a.cps = cdiv(a.C / t.bc, splits);
   a.out = splits > 1 ? slab : (float*)out;
   a.outb = (u16*)out;
-  if (add && splits > 1 && !reduce) return -4;
-  a.slab = splits > 1 ? (long)a.M * a.Nout : 0;
+  if (addend_lost(add, splits, reduce)) return -4;
+  const long n = (long)a.M * a.Nout;
+  a.slab = splits > 1 ? n : 0;
   int rc;
   if (obf && splits == 1)
-    rc = launch_halo_tile<DG, 1, true>(a, tile, splits, st);
+    rc = launch_halo_tile<DG, 1, true>(a, t.id, splits, st);
   else if (np == 3)
-    rc = launch_halo_tile<DG, 3, false>(a, tile, splits, st);
+    rc = launch_halo_tile<DG, 3, false>(a, t.id, splits, st);
   else if (np == 2)
-    rc = launch_halo_tile<DG, 2, false>(a, tile, splits, st);
+    rc = launch_halo_tile<DG, 2, false>(a, t.id, splits, st);
   else
-    rc = launch_halo_tile<DG, 1, false>(a, tile, splits, st);
-  if (rc) return rc;
-  if (splits == 1) return add ? dpa_add_inplace(out, add, (long)a.M * a.Nout, obf, st) : 0;
-  if (!reduce) return 0;
-  const long n4 = (long)a.M * a.Nout / 4;
-  if (obf) return launch_splitk_reduce_t(slab, (ushort4*)out, n4, splits, st, (const ushort4*)add);
-  return launch_splitk_reduce_t(slab, (float4*)out, n4, splits, st, (const float4*)add);
-}
-
-int halo_bytes(unsigned& xb, long xel, unsigned& wb, long wel) {
-  if (xel * 2 >= (1L << 31) || wel * 2 >= (1L << 31)) return -5;
-  xb = (unsigned)(xel * 2);
-  wb = (unsigned)(wel * 2);
-  return 0;
+    rc = launch_halo_tile<DG, 1, false>(a, t.id, splits, st);
+  return rc ? rc : finish_splitk(slab, out, n, splits, reduce, obf, add, st);
 }
 
 template <int NP, int P>
@@ -2059,89 +2210,68 @@ int launch_halo_wgrad(const WHArgs& a, int splits, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-int run_halo_wgrad(WHArgs& a, int tile, int splits, int np, float* dw, float* slab, hipStream_t st) {
-  if (tile != 16 && tile != 17) return -6;
-  const int P = tile == 16 ? 64 : 32;
-  if (a.C % 8 || a.K % 8 || P + 2 * a.W + 2 > halo_wslots(P) - 1) return -6;
+template <int NP>
+int launch_halo_wgrad_tile(const WHArgs& a, int tile, int splits, hipStream_t st) {
+  return with_tile<F_HALO_WGRAD>(tile, [&](auto i) {
+    return launch_halo_wgrad<NP, TILES[decltype(i)::value].bm>(a, splits, st);
+  });
+}
+
+int run_halo_wgrad(const Operands& o, const Geo& g, const Tile& t, int splits, int np, float* dw, float* slab,
+                   hipStream_t st) {
+  WHArgs a = args<WHArgs>(o, XM_WGRAD, g);
+  a.N = g.N;
+  a.H = g.H;
+  a.W = g.W;
+  a.C = g.C;
+  a.K = g.K;
   a.M = a.N * a.H * a.W;
-  if (halo_bytes(a.xbytes, (long)a.M * a.C, a.dzbytes, (long)a.M * a.K)) return -5;
-  a.nchunks = cdiv(a.M, P);
-  a.gk = cdiv(a.K, 128);
-  a.gc = cdiv(a.C, 32);
+  a.nchunks = cdiv(a.M, t.bm);
+  a.gk = cdiv(a.K, t.bn);
+  a.gc = cdiv(a.C, t.bc);
   a.cps = cdiv(a.nchunks, splits);
   a.fd_HW = make_fastdiv(a.H * a.W);
   a.fd_W = make_fastdiv(a.W);
+  const long n = (long)a.K * 9 * a.C;
   a.out = splits > 1 ? slab : dw;
-  a.slab = splits > 1 ? (long)a.K * 9 * a.C : 0;
-  int rc;
-  if (np == 3)
-    rc = P == 64 ? launch_halo_wgrad<3, 64>(a, splits, st) : launch_halo_wgrad<3, 32>(a, splits, st);
-  else if (np == 2)
-    rc = P == 64 ? launch_halo_wgrad<2, 64>(a, splits, st) : launch_halo_wgrad<2, 32>(a, splits, st);
-  else
-    rc = P == 64 ? launch_halo_wgrad<1, 64>(a, splits, st) : launch_halo_wgrad<1, 32>(a, splits, st);
-  if (rc || splits == 1) return rc;
-  return launch_splitk_reduce(slab, dw, (long)a.K * 9 * a.C / 4, splits, st);
+  a.slab = splits > 1 ? n : 0;
+  const int rc = np == 3   ? launch_halo_wgrad_tile<3>(a, t.id, splits, st)
+                 : np == 2 ? launch_halo_wgrad_tile<2>(a, t.id, splits, st)
+                           : launch_halo_wgrad_tile<1>(a, t.id, splits, st);
+  return rc ? rc : finish_splitk(slab, dw, n, splits, 1, 0, nullptr, st);
 }
 
-
-// ---- streaming GEMM tile (1x1 / stride 1 / pad 0 forward, bf16 in and out, one split): id 30 ----
-bool is_stream(int tile) { return tile == 30; }
-
-// -6: the call does not fit the streaming kernel (it is tuned as a candidate alongside the others)
-int run_stream(const u16* x, const u16* w, void* out, int M, int N, int K, int np, int obf, int splits,
-               float* stats, hipStream_t st, bool dgrad = false) {
-  if (np != 1 || !obf || splits != 1 || K % 8 || N % 8) return -6;
+// ---- streaming GEMM tile ----
+// -6: more than one split, or a start signal (the tile is tuned as a candidate alongside the others)
+template <bool DG>
+int run_stream(const Operands& o, const Geo& g, const Tile& t, int splits, void* out, float* stats, const void* add,
+               hipStream_t st) {
+  constexpr int kind = DG ? XM_DGRAD : XM_FPROP;
+  if (splits != 1 || o.sig) return -6;
   SArgs s{};
-  s.x = x;
-  s.w = w;
-  if ((long)M * K * 2 >= (1L << 31) || (long)N * K * 2 >= (1L << 31)) return -5;
-  s.xbytes = (unsigned)((long)M * K * 2);
-  s.wbytes = (unsigned)((long)N * K * 2);
+  s.x = o.x;
+  s.w = o.w;
+  s.xbytes = (unsigned)(g.xel(kind) * 2);
+  s.wbytes = (unsigned)(g.wel(kind) * 2);
   s.out = (u16*)out;
-  s.M = M;
-  s.N = N;
-  s.K = K;
-  s.gm = cdiv(M, 256);
-  s.gn = cdiv(N, 128);
+  s.M = g.N * g.H * g.W;
+  s.N = g.cout(kind);
+  s.K = g.cred(kind);
+  s.gm = cdiv(s.M, t.bm);
+  s.gn = cdiv(s.N, t.bn);
   s.stats = reinterpret_cast<float2*>(stats);
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const int grid = std::min(s.gm * s.gn, 2 * cus);
-  if (dgrad) {
-    gemm_stream_kernel<256, 128, 4, 2, 32, true><<<grid, 512, 0, st>>>(s);
-  } else {
-    gemm_stream_kernel<256, 128, 4, 2, 32, false><<<grid, 512, 0, st>>>(s);
-  }
-  return (int)hipGetLastError();
+  const int rc = with_tile<F_STREAM>(t.id, [&](auto i) {
+    constexpr Tile c = TILES[decltype(i)::value];
+    gemm_stream_kernel<c.bm, c.bn, c.wm, c.wn, c.bc, DG><<<grid, c.wm * c.wn * 64, 0, st>>>(s);
+    return (int)hipGetLastError();
+  });
+  return rc ? rc : finish_splitk(nullptr, out, (long)s.M * s.N, 1, 1, 1, add, st);
 }
 
-// ---- position-major tiles (small images): ids 24-29 ----
-//   24 / 25: 256 rows (32 images x 8 positions) x 128, 4x2 waves, 32-channel chunks, <= 12 staged
-//            pixels (4x4 images), weight tiles 1 / 4 steps ahead
-//   26:      256 rows (64 images x 4 positions) x 128, 4x2 waves, 32-channel chunks, <= 4 staged pixels
-//   27 / 28: 256 rows (64 images x 4 positions) x 64, 4x2 waves of 64x32, 32-channel chunks, <= 4
-//            staged pixels (2x2 images), weight tiles 1 / 4 steps ahead
-//   29:      as 24 with 16-channel chunks
-bool is_pos(int tile) { return tile >= 24 && tile <= 29; }
-int pos_bm(int) { return 256; }
-int pos_ni(int tile) { return (tile >= 26 && tile <= 28) ? 64 : 32; }
-int pos_bn(int tile) { return (tile == 27 || tile == 28) ? 64 : 128; }
-int pos_bc(int tile) { return tile == 29 ? 16 : 32; }
-int pos_nspx(int tile) { return (tile >= 26 && tile <= 28) ? 4 : 12; }
-int pos_waves_m(int) { return 4; }
-
-// staged pixels of the worst position block, or -1 when the positions do not tile the image
-int pos_staged(int H, int W, int ppt) {
-  if (H < 2 || W < 2 || (H * W) % ppt) return -1;
-  int worst = 0;
-  for (int p0 = 0; p0 < H * W; p0 += ppt) {
-    const int ylo = std::max(0, p0 / W - 1), yhi = std::min(H, (p0 + ppt - 1) / W + 2);
-    worst = std::max(worst, (yhi - ylo) * W);
-  }
-  return worst;
-}
-
+// ---- position-major tiles ----
 // Position order of a tile (4 bits per slot): longest-processing-time assignment of the positions of
 // the first position block to the row waves (PPT / waves_m positions each), by in-image tap count.
 unsigned pos_perm(int H, int W, int ppt, int waves_m) {
@@ -2177,39 +2307,36 @@ int launch_pos(const PArgs& a, int splits, hipStream_t st) {
 
 template <bool DG, int NP>
 int launch_pos_tile(const PArgs& a, int tile, int splits, hipStream_t st) {
-  switch (tile) {
-    case 24: return launch_pos<256, 128, 4, 2, DG, NP, 32, 32, 12, 1>(a, splits, st);
-    case 25: return launch_pos<256, 128, 4, 2, DG, NP, 32, 32, 12, 4>(a, splits, st);
-    case 26: return launch_pos<256, 128, 4, 2, DG, NP, 32, 64, 4, 1>(a, splits, st);
-    case 27: return launch_pos<256, 64, 4, 2, DG, NP, 32, 64, 4, 1>(a, splits, st);
-    case 28: return launch_pos<256, 64, 4, 2, DG, NP, 32, 64, 4, 4>(a, splits, st);
-    default: return launch_pos<256, 128, 4, 2, DG, NP, 16, 32, 12, 1>(a, splits, st);
-  }
+  return with_tile<F_POS>(tile, [&](auto i) {
+    constexpr Tile t = TILES[decltype(i)::value];
+    return launch_pos<t.bm, t.bn, t.wm, t.wn, DG, NP, t.bc, t.ni, t.nspx, t.pd>(a, splits, st);
+  });
 }
 
-// -6: the conv does not fit the tile (channels, or more staged pixels than the tile holds)
 template <bool DG>
-int run_pos(PArgs& a, int tile, int splits, int np, int obf, float* slab, void* out, int reduce, hipStream_t st,
-            const void* add = nullptr) {
-  const int BM = pos_bm(tile), NI = pos_ni(tile), BC = pos_bc(tile), ppt = BM / NI;
-  const int ns = pos_staged(a.H, a.W, ppt);
-  if (obf || a.C % BC || a.Nout % 8 || ns < 0 || ns > pos_nspx(tile)) return -6;
-  if (add && splits > 1 && !reduce) return -4;
-  const long M = (long)a.N * a.H * a.W;
+int run_pos(const Operands& o, const Geo& g, const Tile& t, int splits, int np, float* slab, void* out, int reduce,
+            const void* add, hipStream_t st) {
+  constexpr int kind = DG ? XM_DGRAD : XM_FPROP;
+  PArgs a = args<PArgs>(o, kind, g);
+  a.N = g.N;
+  a.H = g.H;
+  a.W = g.W;
+  a.C = g.cred(kind);
+  a.Nout = g.cout(kind);
+  if (addend_lost(add, splits, reduce)) return -4;
+  const int ppt = t.bm / t.ni;
+  const long n = (long)a.N * a.H * a.W * a.Nout;
   a.npb = a.H * a.W / ppt;
-  a.perm = pos_perm(a.H, a.W, ppt, pos_waves_m(tile));
-  a.gm = cdiv(a.N, NI) * a.npb;
-  a.gn = cdiv(a.Nout, pos_bn(tile));
-  a.cps = cdiv(a.C / BC, splits);
+  a.perm = pos_perm(a.H, a.W, ppt, t.wm);
+  a.gm = cdiv(a.N, t.ni) * a.npb;
+  a.gn = cdiv(a.Nout, t.bn);
+  a.cps = cdiv(a.C / t.bc, splits);
   a.out = splits > 1 ? slab : (float*)out;
-  a.slab = splits > 1 ? M * a.Nout : 0;
-  const int rc = np == 3   ? launch_pos_tile<DG, 3>(a, tile, splits, st)
-                 : np == 2 ? launch_pos_tile<DG, 2>(a, tile, splits, st)
-                           : launch_pos_tile<DG, 1>(a, tile, splits, st);
-  if (rc) return rc;
-  if (splits == 1) return add ? dpa_add_inplace(out, add, M * a.Nout, 0, st) : 0;
-  if (!reduce) return 0;
-  return launch_splitk_reduce_t(slab, (float4*)out, M * a.Nout / 4, splits, st, (const float4*)add);
+  a.slab = splits > 1 ? n : 0;
+  const int rc = np == 3   ? launch_pos_tile<DG, 3>(a, t.id, splits, st)
+                 : np == 2 ? launch_pos_tile<DG, 2>(a, t.id, splits, st)
+                           : launch_pos_tile<DG, 1>(a, t.id, splits, st);
+  return rc ? rc : finish_splitk(slab, out, n, splits, reduce, 0, add, st);
 }
 
 }  // namespace
@@ -2218,146 +2345,66 @@ extern "C" {  // arguments: api.h
 int dpa_x3_splits(int Kred, int splits) { return xsplits(Kred, splits); }
 
 int dpa_conv_stats_rows(int tile) {
-  return is_pos(tile) ? 0 : (is_stream(tile) ? 256 : (is_halo(tile) ? halo_bm(tile) : tile_rows(tile)));
+  const Tile* t = find_tile(XM_FPROP, tile);
+  return !t || t->fam == F_POS ? 0 : t->bm;
+}
+
+int dpa_conv_x3_tile_end() {
+  int end = 0;
+  for (const Tile& t : TILES) end = std::max(end, t.id + 1);
+  return end;
+}
+
+int dpa_conv_x3_tile_family(int kind, int tile) {
+  const Tile* t = find_tile(kind, tile);
+  return t ? t->fam : 0;
+}
+
+int dpa_conv_x3_fits(int kind, int tile, int np, int obf, int N, int H, int W, int C, int K, int R, int S, int stride,
+                     int pad) {
+  if (kind != XM_FPROP && kind != XM_DGRAD && kind != XM_WGRAD) return -6;
+  return tile_fits(kind, find_tile(kind, tile), np, obf, make_geo(N, H, W, C, K, R, S, stride, pad));
 }
 
 int dpa_conv_x3_fprop(const u16* x, long xps, const u16* w, long wps, void* out, float* slab, int N, int H, int W,
                       int C, int Kout, int R, int S, int stride, int pad, int splits, int tile, int reduce,
                       int posmajor, int np, int obf, hipStream_t st, float* stats, float oscale,
                       const unsigned* obound) {
-  if (stats && (is_pos(tile) || (is_halo(tile) ? xsplits(9 * C, splits) : xsplits(R * S * C, splits)) > 1)) return -7;
-  if (is_stream(tile)) {
-    if (R != 1 || S != 1 || stride != 1 || pad != 0) return -6;
-    return run_stream(x, w, out, N * H * W, Kout, C, np, obf, xsplits(C, splits), stats, st);
-  }
-  if (is_halo(tile)) {
-    if (stride != 1 || pad != 1 || R != 3 || S != 3) return -6;
-    HArgs h{};
-    h.oscale = oscale;
-    h.obound = obound;
-    h.x = x;
-    h.xps = xps;
-    h.w = w;
-    h.wps = wps;
-    h.N = N;
-    h.H = H;
-    h.W = W;
-    h.C = C;
-    h.Nout = Kout;
-    h.stats = reinterpret_cast<float2*>(stats);
-    if (halo_bytes(h.xbytes, (long)N * H * W * C, h.wbytes, (long)Kout * 9 * C)) return -5;
-    return run_halo<false>(h, tile, xsplits(9 * C, splits), np, obf, slab, out, reduce, st);
-  }
-  if (is_pos(tile)) {
-    if (stride != 1 || pad != 1 || R != 3 || S != 3) return -6;
-    PArgs q{};
-    q.oscale = oscale;
-    q.obound = obound;
-    q.x = x;
-    q.xps = xps;
-    q.w = w;
-    q.wps = wps;
-    q.N = N;
-    q.H = H;
-    q.W = W;
-    q.C = C;
-    q.Nout = Kout;
-    if (halo_bytes(q.xbytes, (long)N * H * W * C, q.wbytes, (long)Kout * 9 * C)) return -5;
-    return run_pos<false>(q, tile, xsplits(9 * C, splits), np, obf, slab, out, reduce, st);
-  }
-  Args a{};
-  a.oscale = oscale;
-  a.obound = obound;
-  a.x = x;
-  a.xps = xps;
-  a.w = w;
-  a.wps = wps;
+  const Geo g = make_geo(N, H, W, C, Kout, R, S, stride, pad);
+  const Tile* t = find_tile(XM_FPROP, tile);
+  if (const int rc = tile_fits(XM_FPROP, t, np, obf, g)) return rc;
+  const Operands o{x, xps, w, wps, oscale, obound, nullptr, 0};
+  const int s = xsplits(R * S * C, splits);
+  if (stats && (t->fam == F_POS || s > 1)) return -7;
+  if (t->fam == F_STREAM) return run_stream<false>(o, g, *t, s, out, stats, nullptr, st);
+  if (t->fam == F_HALO) return run_halo<false>(o, g, *t, s, np, obf, slab, out, reduce, stats, nullptr, st);
+  if (t->fam == F_POS) return run_pos<false>(o, g, *t, s, np, slab, out, reduce, nullptr, st);
+  Args a = args<Args>(o, XM_FPROP, g);
   fill(a, N, H, W, C, R, S, stride, pad);
   a.Nout = Kout;
-  if (C % 8 || Kout % 8) return -2;
-  if (set_bytes(a, (long)N * H * W * C, (long)Kout * a.Ktot)) return -5;
-  a.gm = cdiv(a.M, tile_rows(tile));
-  a.gn = cdiv(Kout, tile_cols(tile));
-  a.splits = xsplits(a.Ktot, splits);
-  a.posmajor = posmajor & 1;
-  a.nmajor = (posmajor >> 1) & 1;
   a.stats = reinterpret_cast<float2*>(stats);
-  a.sepi = ob_epi();
-  if (obf && np != 1) return -4;
-  a.out = a.splits > 1 ? slab : (float*)out;
-  a.outb = (u16*)out;
-  a.slab = a.splits > 1 ? (long)a.M * Kout : 0;
-  const int rc = launch_any<XM_FPROP>(a, tile, np, obf && a.splits == 1, st);
-  if (rc) return rc;
-  if (a.splits > 1 && reduce) {
-    const long n4 = (long)a.M * Kout / 4;
-    if (obf) return launch_splitk_reduce_t(slab, (ushort4*)out, n4, a.splits, st);
-    return launch_splitk_reduce(slab, (float*)out, n4, a.splits, st);
-  }
-  return 0;
+  return run_gemm<XM_FPROP>(a, *t, a.M, Kout, a.Ktot, (long)a.M * Kout, s, posmajor, np, obf, slab, out, reduce,
+                            nullptr, st);
 }
 
 int dpa_conv_x3_dgrad(const u16* dz, long dzps, const u16* w, long wps, void* dx, float* slab, int N, int Hd, int Wd,
                       int K, int C, int R, int S, int stride, int pad, int H, int W, int splits, int tile, int reduce,
                       int posmajor, int np, int obf, hipStream_t st, const void* add, int* sig, int sig_val,
                       float oscale, const unsigned* obound) {
-  if (is_stream(tile)) {  // dX = dZ W for a 1x1 / stride-1 conv (W [K][C] read row-contiguous)
-    if (R != 1 || S != 1 || stride != 1 || pad != 0 || sig) return -6;
-    const int rc = run_stream(dz, w, dx, N * H * W, C, K, np, obf, xsplits(K, splits), nullptr, st, true);
-    if (rc || !add) return rc;
-    return dpa_add_inplace(dx, add, (long)N * H * W * C, obf, st);
-  }
-  if (is_halo(tile)) {
-    if (stride != 1 || pad != 1 || R != 3 || S != 3 || Hd != H || Wd != W) return -6;
-    HArgs h{};
-    h.oscale = oscale;
-    h.obound = obound;
-    h.sig = sig;
-    h.sig_val = sig_val;
-    h.x = dz;
-    h.xps = dzps;
-    h.w = w;
-    h.wps = wps;
-    h.N = N;
-    h.H = H;
-    h.W = W;
-    h.C = K;
-    h.Nout = C;
-    if (halo_bytes(h.xbytes, (long)N * H * W * K, h.wbytes, (long)K * 9 * C)) return -5;
-    return run_halo<true>(h, tile, xsplits(9 * K, splits), np, obf, slab, dx, reduce, st, add);
-  }
-  if (is_pos(tile)) {
-    if (stride != 1 || pad != 1 || R != 3 || S != 3 || Hd != H || Wd != W) return -6;
-    PArgs q{};
-    q.oscale = oscale;
-    q.obound = obound;
-    q.sig = sig;
-    q.sig_val = sig_val;
-    q.x = dz;
-    q.xps = dzps;
-    q.w = w;
-    q.wps = wps;
-    q.N = N;
-    q.H = H;
-    q.W = W;
-    q.C = K;
-    q.Nout = C;
-    if (halo_bytes(q.xbytes, (long)N * H * W * K, q.wbytes, (long)K * 9 * C)) return -5;
-    return run_pos<true>(q, tile, xsplits(9 * K, splits), np, obf, slab, dx, reduce, st, add);
-  }
-  Args a{};
-  a.oscale = oscale;
-  a.obound = obound;
-  a.sig = sig;
-  a.sig_val = sig_val;
-  a.x = dz;
-  a.xps = dzps;
-  a.w = w;
-  a.wps = wps;
-  if (stride < 1 || (stride & (stride - 1)) || R - 1 - pad < 0) return -3;
+  Geo g = make_geo(N, H, W, C, K, R, S, stride, pad);
+  g.P = Hd;
+  g.Q = Wd;
+  const Tile* t = find_tile(XM_DGRAD, tile);
+  if (const int rc = tile_fits(XM_DGRAD, t, np, obf, g)) return rc;
+  const Operands o{dz, dzps, w, wps, oscale, obound, sig, sig_val};
+  const int s = xsplits(R * S * K, splits);
+  // stream: dX = dZ W for a 1x1 / stride-1 conv (W [K][C] read row-contiguous)
+  if (t->fam == F_STREAM) return run_stream<true>(o, g, *t, s, dx, nullptr, add, st);
+  if (t->fam == F_HALO) return run_halo<true>(o, g, *t, s, np, obf, slab, dx, reduce, nullptr, add, st);
+  if (t->fam == F_POS) return run_pos<true>(o, g, *t, s, np, slab, dx, reduce, add, st);
+  Args a = args<Args>(o, XM_DGRAD, g);
   const int padd = R - 1 - pad;  // padding of the dilated-dZ gather
   fill(a, N, Hd, Wd, K, R, S, 1, padd);
-  if (set_bytes(a, (long)N * Hd * Wd * K, (long)K * R * S * C)) return -5;
   const long Mfull = (long)N * H * W;
   // stride 2 with even output sides: phase-decomposed (Args.phase); DPA_DGRAD_PHASE=0 keeps the
   // dilated form (A/B)
@@ -2397,76 +2444,22 @@ int dpa_conv_x3_dgrad(const u16* dz, long dzps, const u16* w, long wps, void* dx
   a.fd_Q = make_fastdiv(a.Q);
   a.fd_PQ = make_fastdiv(a.P * a.Q);
   a.Nout = C;
-  if (C % 8 || K % 8) return -2;
-  a.gm = cdiv(a.M, tile_rows(tile));
-  a.gn = cdiv(C, tile_cols(tile));
-  a.splits = xsplits(a.Ktot, splits);
-  a.posmajor = posmajor & 1;
-  a.nmajor = (posmajor >> 1) & 1;
-  a.sepi = ob_epi();
-  if (obf && np != 1) return -4;
-  a.out = a.splits > 1 ? slab : (float*)dx;
-  a.outb = (u16*)dx;
-  if (add && a.splits > 1 && !reduce) return -4;
-  a.slab = a.splits > 1 ? Mfull * C : 0;
-  const int rc = launch_any<XM_DGRAD>(a, tile, np, obf && a.splits == 1, st);
-  if (rc) return rc;
-  if (a.splits == 1 && add) return dpa_add_inplace(dx, add, Mfull * C, obf, st);
-  if (a.splits > 1 && reduce) {
-    const long n4 = Mfull * C / 4;
-    if (obf) return launch_splitk_reduce_t(slab, (ushort4*)dx, n4, a.splits, st, (const ushort4*)add);
-    return launch_splitk_reduce_t(slab, (float4*)dx, n4, a.splits, st, (const float4*)add);
-  }
-  return 0;
+  return run_gemm<XM_DGRAD>(a, *t, a.M, C, a.Ktot, Mfull * C, splits, posmajor, np, obf, slab, dx, reduce, add, st);
 }
 
 int dpa_conv_x3_wgrad(const u16* x, long xps, const u16* dz, long dzps, float* dw, float* slab, int N, int H, int W,
                       int C, int Kout, int R, int S, int stride, int pad, int splits, int tile, int posmajor, int np,
                       hipStream_t st, float oscale, const unsigned* obound) {
-  if (is_halo(tile)) {
-    if (stride != 1 || pad != 1 || R != 3 || S != 3) return -6;
-    WHArgs h{};
-    h.oscale = oscale;
-    h.obound = obound;
-    h.x = x;
-    h.xps = xps;
-    h.dz = dz;
-    h.dzps = dzps;
-    h.N = N;
-    h.H = H;
-    h.W = W;
-    h.C = C;
-    h.K = Kout;
-    return run_halo_wgrad(h, tile, xsplits(N * H * W, splits), np, dw, slab, st);
-  }
-  Args a{};
-  a.oscale = oscale;
-  a.obound = obound;
-  a.x = x;
-  a.xps = xps;
-  a.w = dz;
-  a.wps = dzps;
+  const Geo g = make_geo(N, H, W, C, Kout, R, S, stride, pad);
+  const Tile* t = find_tile(XM_WGRAD, tile);
+  if (const int rc = tile_fits(XM_WGRAD, t, np, 0, g)) return rc;
+  const Operands o{x, xps, dz, dzps, oscale, obound, nullptr, 0};
+  if (t->fam == F_HALO_WGRAD) return run_halo_wgrad(o, g, *t, xsplits(N * H * W, splits), np, dw, slab, st);
+  Args a = args<Args>(o, XM_WGRAD, g);
   fill(a, N, H, W, C, R, S, stride, pad);
-  if (set_bytes(a, (long)N * H * W * C, (long)a.M * Kout)) return -5;
   a.Nout = Kout;
-  if (C % 8 || Kout % 8) return -2;
-  a.gm = cdiv(Kout, tile_rows(tile));
-  a.gn = cdiv(a.Ktot, tile_cols(tile));
-  a.splits = xsplits(a.M, splits);
-  a.posmajor = posmajor & 1;
-  a.nmajor = (posmajor >> 1) & 1;
-  a.out = a.splits > 1 ? slab : dw;
-  a.slab = a.splits > 1 ? (long)Kout * a.Ktot : 0;
-  a.sepi = ob_epi();
-  const int rc = np == 3   ? launch_tile<XM_WGRAD, 3>(a, tile, st)
-                 : np == 2 ? launch_tile<XM_WGRAD, 2>(a, tile, st)
-                           : launch_tile<XM_WGRAD, 1>(a, tile, st);
-  if (rc) return rc;
-  if (a.splits > 1) {
-    const long n4 = (long)Kout * a.Ktot / 4;
-    return launch_splitk_reduce(slab, dw, n4, a.splits, st);
-  }
-  return 0;
+  return run_gemm<XM_WGRAD>(a, *t, Kout, a.Ktot, a.M, (long)Kout * a.Ktot, splits, posmajor, np, 0, slab, dw, 1, nullptr,
+                            st);
 }
 
 int dpa_split_planes(const float* x, u16* out, long n, long ps, int np, float scale, hipStream_t st) {

@@ -39,6 +39,7 @@ import torch
 from . import _ext
 from .models.vgg import VGGSpec
 from .ops import cpu_ref
+from .ops.functional import conv_tile_candidates
 from .optim import FlatUpdate, ScheduleTensors
 from .utils.arena import Arena
 from .utils.streams import DevEvent, StreamJoin
@@ -101,50 +102,19 @@ def conv_key(impl: str, kind: str, n: int, hw: int, cin: int, cout: int) -> str:
     return f"{impl}|{kind}|{n}|{hw}|{cin}|{cout}"
 
 
-# Halo-staged 3x3/s1/p1 tiles of conv_x3.hip (ids after the 16 implicit-GEMM tiles): the block's
-# input pixels are staged once per channel chunk and the 9 taps read shifted views of them.
-HALO_TILES = (16, 17, 18, 19, 20, 21, 22, 23)  # fprop / dgrad: 256 or 128 pixels x 128 (16-19, 22) or 64
-                                               # (20, 21, 23) output channels, 16-, 32- or 64-channel
-                                               # chunks (22, 23: not x3's 3 planes; h2 rows <= 16 pixels)
-# tile -> (rows BM, channel chunk BC) of conv_x3.hip's halo_bm / halo_bc (image slots: halo_slots)
-HALO_GEOM = {16: (256, 16), 17: (256, 32), 18: (128, 16), 19: (128, 32), 20: (256, 32), 21: (128, 32),
-             22: (256, 64), 23: (256, 64)}
-HALO_WGRAD_TILES = (16, 17)          # wgrad: 64- or 32-pixel chunks, 128 x 32 x 9 taps per block
-POS_TILES = (24, 25, 26, 27, 28, 29)  # fprop / dgrad of small images: position-major rows, padding taps
-                                      # skipped (conv_x3.hip conv_pos_kernel)
-
-
 def halo_ok(kind: str, tile: int, w: int, cred: int, cout: int = 8, np_: int = 2) -> bool:
     """Whether halo tile `tile` runs conv call `kind` of a 3x3/s1/p1 conv whose rows are w pixels
     wide.  cred: channels reduced (fprop C_in, dgrad C_out; wgrad C_in), cout: output channels
-    (wgrad C_out), np_: operand planes (1 bf16, 2 h2, 3 x3).  Mirrors run_halo / run_halo_wgrad in
-    conv_x3.hip (-6 otherwise)."""
-    if kind == "wgrad":
-        p = {16: 64, 17: 32}.get(tile)
-        return p is not None and cred % 8 == 0 and cout % 8 == 0 and p + 2 * w + 2 <= 2 * p + 3
-    if tile not in HALO_TILES:
-        return False
-    bm, bc = HALO_GEOM[tile]
-    slots = bm + 35 if bc >= 64 and np_ >= 2 else bm + bm // 2 + 1
-    if bc >= 64 and np_ == 3:
-        return False
-    return cred % bc == 0 and cout % 8 == 0 and bm + 2 * w + 2 <= slots - 1
+    (wgrad C_out), np_: operand planes (1 bf16, 2 h2, 3 x3).  The launcher's own answer."""
+    cin, k = (cout, cred) if kind == "dgrad" else (cred, cout)
+    return tile in conv_tile_candidates(kind, (1, w, w, cin, k, 3, 3, 1, 1), np_, ("halo", "halo_wgrad"))
 
 
 def pos_ok(kind: str, tile: int, h: int, w: int, cred: int, cout: int) -> bool:
-    """Whether position-major tile `tile` runs conv call `kind` (fprop / dgrad of a 3x3/s1/p1 conv)
-    on h x w images; mirrors run_pos in conv_x3.hip (-6 otherwise)."""
-    if kind == "wgrad" or tile not in POS_TILES or h < 2 or w < 2:
-        return False
-    bm = 256
-    ni = 64 if tile in (26, 27, 28) else 32
-    bc = 16 if tile == 29 else 32
-    nspx = 4 if tile in (26, 27, 28) else 12
-    ppt = bm // ni
-    if (h * w) % ppt or cred % bc or cout % 8:
-        return False
-    worst = max((min(h, (p0 + ppt - 1) // w + 2) - max(0, p0 // w - 1)) * w for p0 in range(0, h * w, ppt))
-    return worst <= nspx
+    """Whether position-major tile `tile` runs conv call `kind` of a 3x3/s1/p1 conv on h x w
+    images (cred / cout as for halo_ok).  The launcher's own answer."""
+    cin, k = (cout, cred) if kind == "dgrad" else (cred, cout)
+    return tile in conv_tile_candidates(kind, (1, h, w, cin, k, 3, 3, 1, 1), 1, ("pos",))
 
 
 class VGGEngine(ScheduleTensors):
@@ -583,19 +553,17 @@ class VGGEngine(ScheduleTensors):
     def conv_candidates(self, i: int, kind: str):
         impl = self._layer_impl(i)
         l = self.spec.convs[i]
-        tiles = (0, 1) if impl == "fp32" else tuple(range(16))
         splits = (1, 2, 4, 8, 16, 32, 64, 128, 256, 512) if kind == "wgrad" else (1, 2, 4, 8, 16)
-        pms = (0, 1) if impl == "fp32" else (0, 1, 2, 3)  # x3 tiles: bit 1 = column-tile-outer block order
-        out = [(t, s, pm) for t in tiles for s in splits for pm in pms]
-        if impl != "fp32":  # halo tiles ignore the row order flag
-            if kind == "wgrad":
-                ok = [t for t in HALO_WGRAD_TILES if halo_ok(kind, t, l.hw, l.cin_pad, l.cout)]
-            else:
-                cred, cout = (l.cin_pad, l.cout) if kind == "fprop" else (l.cout, l.cin_pad)
-                np_ = {"x3": 3, "h2": 2}.get(impl, 1)
-                ok = [t for t in HALO_TILES if halo_ok(kind, t, l.hw, cred, cout, np_)]
-                ok += [t for t in POS_TILES if pos_ok(kind, t, l.hw, l.hw, cred, cout)]
-            out += [(t, s, False) for t in ok for s in splits]
+        if impl == "fp32":  # conv_gemm.hip's two tiles
+            return [(t, s, pm) for t in (0, 1) for s in splits for pm in (0, 1)]
+        geom = (self.max_batch, l.hw, l.hw, l.cin_pad, l.cout, 3, 3, 1, 1)
+        np_ = {"x3": 3, "h2": 2}.get(impl, 1)
+        # implicit-GEMM tiles: posmajor bit 1 = column-tile-outer block order; the halo and
+        # position-major tiles ignore the row order flag
+        out = [(t, s, pm) for t in conv_tile_candidates(kind, geom, np_, ("gemm",)) for s in splits
+               for pm in (0, 1, 2, 3)]
+        out += [(t, s, False) for t in conv_tile_candidates(kind, geom, np_, ("halo", "halo_wgrad", "pos"))
+                for s in splits]
         return out
 
     def autotune(self, n: Optional[int] = None, iters: int = 3, verbose: bool = False,

@@ -107,7 +107,6 @@ TABLE_PATH = os.environ.get("DPA_GENERIC_TABLE") or os.path.join(
 _table: Optional[Dict[str, list]] = None
 _chosen: Dict[str, Tuple[int, int, bool]] = {}
 _AUTOTUNE = {"on": os.environ.get("DPA_AUTOTUNE", "0") == "1", "dirty": False}
-N_TILES = 16
 
 
 def set_autotune(on: bool):
@@ -139,45 +138,34 @@ def save_tuning_table(path: Optional[str] = None):
     _AUTOTUNE["dirty"] = False
 
 
-def halo_candidates(kind: str, geom: tuple, np_: int = 1) -> Tuple[int, ...]:
-    """Halo-staged tiles (conv_x3.hip, ids >= 16) that can run this conv call: 3x3, stride 1,
-    pad 1 only, channel / row-width / plane-count limits as in engine.halo_ok."""
-    from ..engine import HALO_TILES, HALO_WGRAD_TILES, halo_ok
-
-    N, H, W, C, K, R, S, stride, pad = geom
-    if (R, S, stride, pad) != (3, 3, 1, 1):
-        return ()
-    if kind == "wgrad":
-        return tuple(t for t in HALO_WGRAD_TILES if halo_ok("wgrad", t, W, C, K))
-    cred, cout = (C, K) if kind == "fprop" else (K, C)
-    return tuple(t for t in HALO_TILES if halo_ok(kind, t, W, cred, cout, np_))
-
-
-STREAM_TILES = (30,)  # conv_x3.hip gemm_stream_kernel: 1x1 / stride 1 / pad 0 fprop + dgrad, bf16, one split
-
-
-def stream_candidates(impl: str, kind: str, geom: tuple) -> Tuple[int, ...]:
-    """The persistent streaming-GEMM tile when it can run this conv call."""
-    N, H, W, C, K, R, S, stride, pad = geom
-    ok = (impl == "bf16" and kind in ("fprop", "dgrad") and (R, S, stride, pad) == (1, 1, 1, 0) and C % 8 == 0
-          and K % 8 == 0)
-    return STREAM_TILES if ok else ()
+def conv_tile_candidates(kind: str, geom: tuple, np_: int, families: Tuple[str, ...],
+                         obf: bool = False) -> Tuple[int, ...]:
+    """The tiles of the wanted families ("gemm", "halo", "halo_wgrad", "pos", "stream") that run
+    conv call `kind` ("fprop" / "dgrad" / "wgrad") of geom = (N, H, W, C, K, R, S, stride, pad) with
+    np_ operand planes and fp32 or (obf) bf16 output, in id order.  The catalog and the rule are the
+    launcher's own (conv_x3.hip TILES / tile_fits)."""
+    Kx = _ext.require()
+    return tuple(t for t, fam in Kx.conv_tile_catalog(kind)
+                 if fam in families and Kx.conv_tile_fits(kind, t, np_, *geom, obf=obf) == 0)
 
 
 def _autotune(key: str, kind: str, red: int, run: Callable[[int, int, bool], None],
-              slab_bytes: Callable[[int], int], extra_tiles: Tuple[int, ...] = ()) -> Tuple[int, int, bool]:
+              slab_bytes: Callable[[int], int], tiles: Tuple[int, ...],
+              one_split: Tuple[int, ...] = ()) -> Tuple[int, int, bool]:
+    """Time every (tile, splits, posmajor) of `tiles`; the `one_split` tiles (the streaming GEMM)
+    take one split and the NHWC row order only."""
     Kx = _ext.require()
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     best = None
     splits = (1, 2, 4, 8, 16, 32, 64, 128, 256) if kind == "wgrad" else (1, 2, 4, 8, 16)
     seen = set()
-    for tile in tuple(range(N_TILES)) + tuple(extra_tiles):
+    for tile in tiles:
         for s0 in splits:
             s = Kx.x3_splits(red, s0)
             for pm in (False, True):
                 if (tile, s, pm) in seen or slab_bytes(s) > (512 << 20):
                     continue
-                if tile in STREAM_TILES and (s > 1 or pm):  # one split, NHWC row order only
+                if tile in one_split and (s > 1 or pm):
                     continue
                 seen.add((tile, s, pm))
                 try:
@@ -208,8 +196,12 @@ def choose_config(impl: str, kind: str, geom: tuple, M: int, Ngemm: int, Kred: i
     if t is not None:
         c = (int(t[0]), int(t[1]), bool(t[2]))
     elif _AUTOTUNE["on"] and run is not None:
+        # the generic path tunes the implicit-GEMM and halo tiles, and with bf16 activations (bf16
+        # outputs of fprop / dgrad) the streaming GEMM
+        np_, obf = {"x3": 3, "h2": 2}.get(impl, 1), impl == "bf16" and kind != "wgrad"
+        stream = conv_tile_candidates(kind, geom, np_, ("stream",), obf) if impl == "bf16" else ()
         c = _autotune(key, kind, M if kind == "wgrad" else Kred, run, slab_bytes,
-                      halo_candidates(kind, geom, {"x3": 3, "h2": 2}.get(impl, 1)) + stream_candidates(impl, kind, geom))
+                      conv_tile_candidates(kind, geom, np_, ("gemm", "halo", "halo_wgrad"), obf) + stream, stream)
     else:
         c = conv_config(kind, M, Ngemm, Kred, hw_small)
     _chosen[key] = c

@@ -273,13 +273,14 @@ def test_fused_step_matches_single_update(mode, monkeypatch):
 
 
 def test_halo_tile_geometry_rules():
-    """engine.halo_ok mirrors conv_x3.hip run_halo: 64-channel-chunk tiles (22, 23) need C % 64,
-    never run x3's three planes, and with fp16 pairs stage rows of at most 16 pixels (one bf16 plane
-    keeps the BM/4 - 1 limit of the other tiles)."""
-    from distributed_pytorch_amd.engine import HALO_GEOM, halo_ok
+    """The halo rule of conv_x3.hip (engine.halo_ok asks the extension; host code, no launch):
+    64-channel-chunk tiles (22, 23) need C % 64, never run x3's three planes, and with fp16 pairs
+    stage rows of at most 16 pixels (one bf16 plane keeps the BM/4 - 1 limit of the other tiles)."""
+    from distributed_pytorch_amd import _ext
+    from distributed_pytorch_amd.engine import halo_ok
 
     for t in (22, 23):
-        assert HALO_GEOM[t] == (256, 64)
+        assert _ext.require().conv_stats_rows(t) == 256
         assert halo_ok("fprop", t, 16, 64, 128, 2) and not halo_ok("fprop", t, 17, 64, 128, 2)
         assert halo_ok("fprop", t, 56, 64, 64, 1) and not halo_ok("fprop", t, 64, 64, 64, 1)
         assert not halo_ok("fprop", t, 8, 64, 128, 3)

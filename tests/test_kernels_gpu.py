@@ -384,15 +384,20 @@ HALO_SHAPES = [
 ]
 
 
-def _halo_ok(kind, tile, w, cred, cout, np_=2):
-    from distributed_pytorch_amd.engine import halo_ok
+HALO_TILES = [16, 17, 18, 19, 20, 21, 22, 23]
+HALO_WGRAD_SHAPES = HALO_SHAPES + [(4, 32, 32, 8, 64)]
 
-    return halo_ok(kind, tile, w, cred, cout, np_)
+
+def _fits(kind, tile, np_, shape, obf=False):
+    """Whether the launcher admits `tile` for call `kind` of the forward conv `shape` = (N, H, W, C,
+    K[, R, stride, pad]; 3x3 / stride 1 / pad 1 when left out): the extension's own rule."""
+    N, H, W, Cin, K, R, st, pd = tuple(shape) + (3, 1, 1)[len(shape) - 5:]
+    return _C().conv_tile_fits(kind, tile, np_, N, H, W, Cin, K, R, R, st, pd, obf) == 0
 
 
 @pytest.mark.parametrize("shape", HALO_SHAPES)
 @pytest.mark.parametrize("splits", [1, 3])
-@pytest.mark.parametrize("tile", [16, 17, 18, 19, 20, 21, 22, 23])
+@pytest.mark.parametrize("tile", HALO_TILES)
 @pytest.mark.parametrize("np_", [3, 2, 1])
 @pytest.mark.parametrize("dgrad", [False, True])
 def test_conv_halo(shape, splits, tile, np_, dgrad):
@@ -401,8 +406,7 @@ def test_conv_halo(shape, splits, tile, np_, dgrad):
     32- and 64-channel chunks and split-K."""
     C = _C()
     N, H, W, Cin, K = shape
-    cred, cout = (K, Cin) if dgrad else (Cin, K)
-    if not _halo_ok("dgrad" if dgrad else "fprop", tile, W, cred, cout, np_):
+    if not _fits("dgrad" if dgrad else "fprop", tile, np_, shape):
         pytest.skip("shape outside this halo tile")
     g = torch.Generator().manual_seed(17)
     x = torch.randn(N, Cin, H, W, generator=g, dtype=torch.float64).requires_grad_(dgrad)
@@ -428,7 +432,7 @@ def test_conv_halo(shape, splits, tile, np_, dgrad):
         assert rel_err(dx.permute(0, 3, 1, 2), gx) < tol
 
 
-@pytest.mark.parametrize("shape", HALO_SHAPES + [(4, 32, 32, 8, 64)])
+@pytest.mark.parametrize("shape", HALO_WGRAD_SHAPES)
 @pytest.mark.parametrize("splits", [1, 5])
 @pytest.mark.parametrize("tile", [16, 17])
 @pytest.mark.parametrize("np_", [3, 2, 1])
@@ -436,7 +440,7 @@ def test_conv_halo_wgrad(shape, splits, tile, np_):
     """Halo-staged 3x3 weight gradient (tiles 16/17: 64/32-pixel chunks) against fp64."""
     C = _C()
     N, H, W, Cin, K = shape
-    if not _halo_ok("wgrad", tile, W, Cin, K):
+    if not _fits("wgrad", tile, np_, shape):
         pytest.skip("shape outside this halo tile")
     g = torch.Generator().manual_seed(18)
     x = torch.randn(N, Cin, H, W, generator=g, dtype=torch.float64)
@@ -503,15 +507,17 @@ POS_SHAPES = [
 ]
 
 
-def _pos_ok(kind, tile, h, w, cred, cout):
-    from distributed_pytorch_amd.engine import pos_ok
+POS_TILES = [24, 25, 26, 27, 28, 29]
 
-    return pos_ok(kind, tile, h, w, cred, cout)
+
+def _pos_twin(tile):
+    """The halo tile with the same channel chunk (16 / 32) as a position-major tile."""
+    return 18 if tile == 29 else 19
 
 
 @pytest.mark.parametrize("shape", POS_SHAPES)
 @pytest.mark.parametrize("splits", [1, 4])
-@pytest.mark.parametrize("tile", [24, 25, 26, 27, 28, 29])
+@pytest.mark.parametrize("tile", POS_TILES)
 @pytest.mark.parametrize("np_", [3, 2, 1])
 @pytest.mark.parametrize("dgrad", [False, True])
 def test_conv_pos(shape, splits, tile, np_, dgrad):
@@ -520,9 +526,8 @@ def test_conv_pos(shape, splits, tile, np_, dgrad):
     skipped tap only adds exact zeros there)."""
     C = _C()
     N, H, W, Cin, K = shape
-    cred, cout = (K, Cin) if dgrad else (Cin, K)
     kind = "dgrad" if dgrad else "fprop"
-    if not _pos_ok(kind, tile, H, W, cred, cout):
+    if not _fits(kind, tile, np_, shape):
         pytest.skip("shape outside this tile")
     g = torch.Generator().manual_seed(19)
     x = torch.randn(N, Cin, H, W, generator=g, dtype=torch.float64).requires_grad_(dgrad)
@@ -530,7 +535,7 @@ def test_conv_pos(shape, splits, tile, np_, dgrad):
     y = F.conv2d(x, w, padding=1)
     w3 = _planes(w.float().permute(0, 2, 3, 1), np_)
     tol = 1e-5 if np_ in (2, 3) else 2e-2
-    halo = 18 if tile == 29 else 19  # the halo tile with the same channel chunk (16 / 32)
+    halo = _pos_twin(tile)
     outs = []
     for t in (tile, halo):
         if not dgrad:
@@ -551,7 +556,7 @@ def test_conv_pos(shape, splits, tile, np_, dgrad):
     else:
         (ref,) = torch.autograd.grad(y, x, dy)
     assert rel_err(outs[0].permute(0, 3, 1, 2), ref) < tol
-    if _halo_ok(kind, halo, W, cred, cout):
+    if _fits(kind, halo, np_, shape):
         assert torch.equal(outs[0], outs[1])
 
 
@@ -575,8 +580,11 @@ EPI_SHAPES = [
 ]
 
 
+EPI_TILES = [0, 1, 5, 7, 11, 14, 16, 17, 18, 19, 20, 21, 22, 23]
+
+
 @pytest.mark.parametrize("shape", EPI_SHAPES)
-@pytest.mark.parametrize("tile", [0, 1, 5, 7, 11, 14, 16, 17, 18, 19, 20, 21, 22, 23])
+@pytest.mark.parametrize("tile", EPI_TILES)
 @pytest.mark.parametrize("np_", [1, 2, 3])
 @pytest.mark.parametrize("posmajor", [0, 1])
 def test_conv_epilogue_bn_stats(shape, tile, np_, posmajor):
@@ -586,7 +594,7 @@ def test_conv_epilogue_bn_stats(shape, tile, np_, posmajor):
     rounding of the stored values' statistics)."""
     C_ = _C()
     N, H, W, Cin, K, R, st, pd = shape
-    if tile >= 16 and (R != 3 or st != 1 or not _halo_ok("fprop", tile, W, Cin, K, np_)):
+    if tile >= 16 and not _fits("fprop", tile, np_, shape, obf=np_ == 1):
         pytest.skip("halo tiles are 3x3/s1 only")
     if tile >= 16 and posmajor:
         pytest.skip("halo tiles ignore the row order")
@@ -623,6 +631,87 @@ def test_conv_epilogue_stats_refused_with_split_k():
     slab = torch.empty(4 * out.numel(), device="cuda")
     with pytest.raises(RuntimeError):
         C_.conv_x3_fprop(x3, w3, out, slab, 1, 1, 4, 0, True, 0, torch.empty(2 * 64 * 64, device="cuda"))
+
+
+# ----------------------------------------------------------------- the tile catalog and its admission rule
+def test_parametrized_conv_cases_that_run():
+    """How many cases of the parametrized tile tests above the launcher's rule admits (the rest
+    skip): pinned, so a drift of the rule fails here instead of skipping cases there."""
+    kinds = ("fprop", "dgrad")
+    halo = sum(_fits(k, t, np_, sh) for sh in HALO_SHAPES for _ in (1, 3) for t in HALO_TILES for np_ in (3, 2, 1)
+               for k in kinds)
+    wgrad = sum(_fits("wgrad", t, np_, sh) for sh in HALO_WGRAD_SHAPES for _ in (1, 5) for t in (16, 17)
+                for np_ in (3, 2, 1))
+    pos = [(k, t, np_, sh) for sh in POS_SHAPES for _ in (1, 4) for t in POS_TILES for np_ in (3, 2, 1) for k in kinds
+           if _fits(k, t, np_, sh)]
+    bitwise = sum(_fits(k, _pos_twin(t), np_, sh) for k, t, np_, sh in pos)
+    epi = sum(tile < 16 or (not pm and _fits("fprop", tile, np_, sh, obf=np_ == 1))
+              for sh in EPI_SHAPES for tile in EPI_TILES for np_ in (1, 2, 3) for pm in (0, 1))
+    assert (halo, wgrad, len(pos), bitwise, epi) == (756, 114, 180, 180, 184)
+
+
+def test_tile_rule_is_the_launchers_rule():
+    """What conv_tile_fits refuses, the launcher refuses too, loudly and before it launches
+    anything: a tile outside the catalog, or one of another call kind, is no silent default tile."""
+    C = _C()
+    bf = dict(device="cuda", dtype=torch.bfloat16)
+
+    def planes(np_, *shape):
+        return torch.zeros(np_, *shape, **bf)
+
+    cases = [  # kind, tile, np, (N, H, W, C, K)
+        ("fprop", 16, 1, (1, 8, 8, 24, 16)),    # 24 channels: not a multiple of the 16-channel chunk
+        ("fprop", 25, 1, (32, 8, 8, 32, 32)),   # 8x8 images: more than 12 staged pixels
+        ("fprop", 22, 3, (1, 8, 8, 64, 16)),    # three planes of a 64-channel chunk
+        ("wgrad", 24, 1, (32, 4, 4, 32, 32)),   # position-major tiles have no weight gradient
+        ("wgrad", 30, 1, (1, 8, 8, 32, 32)),
+        ("fprop", 31, 1, (1, 8, 8, 32, 32)),    # ids the catalog does not hold
+        ("dgrad", 99, 1, (1, 8, 8, 32, 32)),
+        ("wgrad", -1, 1, (1, 8, 8, 32, 32)),
+    ]
+    for kind, tile, np_, (N, H, W, Cin, K) in cases:
+        assert C.conv_tile_fits(kind, tile, np_, N, H, W, Cin, K, 3, 3, 1, 1) != 0, (kind, tile)
+        x3, z3, w3 = planes(np_, N, H, W, Cin), planes(np_, N, H, W, K), planes(np_, K, 3, 3, Cin)
+        out = torch.full({"fprop": (N, H, W, K), "dgrad": (N, H, W, Cin), "wgrad": (K, 3, 3, Cin)}[kind], 7.0,
+                         device="cuda")
+        with pytest.raises(RuntimeError):
+            if kind == "fprop":
+                C.conv_x3_fprop(x3, w3, out, None, 1, 1, 1, tile, True, False)
+            elif kind == "dgrad":
+                C.conv_x3_dgrad(z3, w3, out, None, 1, 1, 1, tile, True, False)
+            else:
+                C.conv_x3_wgrad(x3, z3, out, None, 1, 1, 1, tile, False)
+        torch.cuda.synchronize()
+        assert bool((out == 7.0).all()), (kind, tile)
+
+
+def test_shipped_plans_are_admitted():
+    """Every bf16-plane entry of the two committed tuning tables names a tile that the rule admits
+    for its conv call (engine keys impl|kind|n|hw|cin|cout: 3x3 / stride 1 / pad 1, fp32 outputs;
+    generic keys impl|kind|N|H|W|C|K|R|S|stride|pad: bf16 outputs of the bf16 fprop / dgrad)."""
+    import json
+    import os
+
+    import distributed_pytorch_amd as pkg
+
+    C = _C()
+    n = 0
+    for name in ("mi355x.json", "generic_mi355x.json"):
+        with open(os.path.join(os.path.dirname(pkg.__file__), "tuning", name)) as f:
+            table = json.load(f)
+        for key, plan in table.items():
+            impl, kind, *g = key.split("|")
+            if impl == "fp32":
+                continue
+            g = [int(v) for v in g]
+            if name == "mi355x.json":
+                (N, hw, cin, cout), obf = g, False
+                g = [N, hw, hw, cin, cout, 3, 3, 1, 1]
+            else:
+                obf = impl == "bf16" and kind != "wgrad"
+            assert C.conv_tile_fits(kind, int(plan[0]), {"x3": 3, "h2": 2, "bf16": 1}[impl], *g, obf) == 0, (key, plan)
+            n += 1
+    assert n > 100  # the tables hold 75 + 68 entries
 
 
 @pytest.mark.parametrize("shape", [(8, 56, 56, 64, 256), (4, 14, 14, 1024, 256), (2, 7, 7, 2048, 512),

@@ -18,7 +18,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from distributed_pytorch_amd.engine import VGGEngine, conv_key, halo_ok  # noqa: E402
+from distributed_pytorch_amd.engine import VGGEngine, conv_key  # noqa: E402
+from distributed_pytorch_amd.ops.functional import conv_tile_candidates  # noqa: E402
 
 
 def main():
@@ -51,12 +52,13 @@ def main():
             if a.only and not any(o in conv_key(impl, kind, n, l.hw, l.cin_pad, l.cout) for o in a.only.split(",")):
                 continue
             cur = e.conv_config(i, kind, n)
-            cred, cout = (l.cin_pad, l.cout) if kind == "fprop" else (l.cout, l.cin_pad)
-            if not (16 <= cur[0] <= 23 or (a.all and halo_ok(kind, 22, l.hw, cred, cout, np_))):
+            cred = l.cin_pad if kind == "fprop" else l.cout
+            halo = conv_tile_candidates(kind, (n, l.hw, l.hw, l.cin_pad, l.cout, 3, 3, 1, 1), np_, ("halo",))
+            if not (16 <= cur[0] <= 23 or (a.all and 22 in halo)):
                 continue
             cands = [cur]
             for tile in (22, 23):
-                if not halo_ok(kind, tile, l.hw, cred, cout, np_):
+                if tile not in halo:
                     continue
                 for s in (1, 2, 4, 8):
                     es = e.K.x3_splits(9 * cred, s)

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from distributed_pytorch_amd import _ext  # noqa: E402
-from distributed_pytorch_amd.engine import halo_ok  # noqa: E402
+from distributed_pytorch_amd.ops.functional import conv_tile_candidates  # noqa: E402
 
 GEOMS = [(56, 64), (28, 128), (14, 256), (7, 512)]  # stride-1 3x3 convs of the bottlenecks: (H = W, C = K)
 
@@ -49,8 +49,8 @@ def main():
             if t is None:
                 continue
             cur = (int(t[0]), int(t[1]), int(bool(t[2])))
-            plans = [cur] + [(tile, s, 0) for tile in (22, 23) for s in (1, 2, 4)
-                             if halo_ok(kind, tile, hw, c, c, 1) and c // 64 >= s]
+            halo = conv_tile_candidates(kind, (n, hw, hw, c, c, 3, 3, 1, 1), 1, ("halo",), obf=True)
+            plans = [cur] + [(tile, s, 0) for tile in (22, 23) for s in (1, 2, 4) if tile in halo and c // 64 >= s]
 
             def run(p):
                 tile, s, pm = p
