@@ -176,6 +176,10 @@ int dpa_spin(long long usec, int* done, hipStream_t s);
 // label_smoothing (0 <= eps < 1, checked by the caller) and target2 [B] / lam [B] (Mixup / CutMix pair
 // targets, both or neither, else -2) pick the row kernel's target mode (ce_target.h: pair, smoothed or
 // plain); only the row kernel sees them (the weight gradient reads dlogits and loss_row).
+// Ranges (Cin % 4 == 0; outside them -2 before any launch): J <= 16, Cin <= 1024, B * J * 4 <= 48 KB:
+// the one-row-per-wave kernels; every other 10 < J <= 1024, Cin <= 1024, any B: the wide kernels (fp32
+// MFMA rows, dpa_gemm_f32 weight gradient).  bn_z never changes which kernels run.  dpa_fc_ce_eval:
+// J <= 16 the former, 16 < J <= 1024 the wide kernel.
 int dpa_fc_ce_train(const float* x, const float* w, const float* b, const long long* target, float* loss_row,
                     float* dlogits, float* dx, float* dw, float* db, float* loss_out, float* loss_accum, int B,
                     int Cin, int J, hipStream_t st, const float* bn_z, const float* bn_scale,

@@ -1,2 +1,2 @@
-from .cifar import (MEAN, STD, DeviceLoader, ImageSet, ShardSampler, get_datasets, load_cifar10,  # noqa: F401
-                    synthetic_cifar)
+from .cifar import (MEAN, NUM_CLASSES, STD, DeviceLoader, ImageSet, ShardSampler, get_datasets,  # noqa: F401
+                    load_cifar10, load_cifar100, synthetic_cifar)

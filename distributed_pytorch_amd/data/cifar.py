@@ -122,13 +122,40 @@ def load_cifar10(root: str, train: bool) -> ImageSet:
     raise FileNotFoundError(f"no CIFAR-10 under {root} (expected cifar-10-batches-bin/ or cifar-10-batches-py/)")
 
 
-def get_datasets(data_root: Optional[str], synthetic: bool, train_size: int = 50000, test_size: int = 10000):
+def load_cifar100(root: str, train: bool) -> ImageSet:
+    """Load CIFAR-100 (fine labels) from ``root``: the binary release (``cifar-100-binary/train.bin`` /
+    ``test.bin``, records of coarse label, fine label, 3072 pixels) or the python release
+    (``cifar-100-python/train`` / ``test``); raises FileNotFoundError."""
+    name = "train" if train else "test"
+    b = os.path.join(root, "cifar-100-binary")
+    if os.path.isdir(b):
+        raw = np.fromfile(os.path.join(b, name + ".bin"), dtype=np.uint8).reshape(-1, 3074)
+        labels = torch.from_numpy(raw[:, 1].astype(np.int64))
+        imgs = torch.from_numpy(raw[:, 2:].reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1).copy())
+        return ImageSet(imgs, labels, "cifar100")
+    p = os.path.join(root, "cifar-100-python")
+    if os.path.isdir(p):
+        d = safe_load_batch(os.path.join(p, name))
+        x = np.asarray(d[b"data"], dtype=np.uint8).reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1).copy()
+        return ImageSet(torch.from_numpy(x), torch.tensor(list(d[b"fine_labels"]), dtype=torch.int64), "cifar100")
+    raise FileNotFoundError(f"no CIFAR-100 under {root} (expected cifar-100-binary/ or cifar-100-python/)")
+
+
+NUM_CLASSES = {"cifar10": 10, "cifar100": 100}
+
+
+def get_datasets(data_root: Optional[str], synthetic: bool, train_size: int = 50000, test_size: int = 10000,
+                 dataset: str = "cifar10"):
+    """(train, test) of ``dataset`` from ``data_root``, or synthetic data with the dataset's class count
+    when asked for or when no files are found."""
+    nc = NUM_CLASSES[dataset]
+    load = load_cifar100 if dataset == "cifar100" else load_cifar10
     if not synthetic and data_root:
         try:
-            return load_cifar10(data_root, True), load_cifar10(data_root, False)
+            return load(data_root, True), load(data_root, False)
         except FileNotFoundError:
             pass
-    return synthetic_cifar(train_size, 0), synthetic_cifar(test_size, 1)
+    return synthetic_cifar(train_size, 0, num_classes=nc), synthetic_cifar(test_size, 1, num_classes=nc)
 
 
 class ShardSampler:

@@ -24,7 +24,7 @@ from typing import Optional
 import torch
 
 from .accum import AccumulatedStep, updates_per_epoch, validate_args
-from .data import DeviceLoader, ShardSampler, get_datasets
+from .data import NUM_CLASSES, DeviceLoader, ShardSampler, get_datasets
 from .engine import VGGEngine
 from .graph_step import GraphedStep
 from .parallel import DistContext, env_dict, init_cli, init_env, init_single, make_sync
@@ -228,6 +228,8 @@ def add_common_args(ap: argparse.ArgumentParser):
     g.add_argument("--lr-gamma", type=float, default=0.1)
     g.add_argument("--seed", type=int, default=1)
     g.add_argument("--sampler-seed", type=int, default=0)
+    g.add_argument("--dataset", default="cifar10", choices=sorted(NUM_CLASSES),
+                   help="the dataset, and with it the classifier head's class count (cifar100: 100 classes)")
     g.add_argument("--data-root", default="./data")
     g.add_argument("--synthetic", action="store_true", help="synthetic CIFAR-shaped data (default if no dataset)")
     g.add_argument("--train-size", type=int, default=50000)
@@ -301,7 +303,8 @@ def build_engine(args, device) -> VGGEngine:
                      weight_decay=args.weight_decay, impl=args.impl, optimizer=getattr(args, "optimizer", None),
                      trust_coef=getattr(args, "trust_coef", None), lars_eps=getattr(args, "lars_eps", 1e-9),
                      clip_grad_norm=getattr(args, "clip_grad_norm", None),
-                     label_smoothing=getattr(args, "label_smoothing", None))
+                     label_smoothing=getattr(args, "label_smoothing", None),
+                     num_classes=NUM_CLASSES[getattr(args, "dataset", "cifar10")])
 
 
 def run(ctx: DistContext, mode: str, args):
@@ -309,7 +312,8 @@ def run(ctx: DistContext, mode: str, args):
     if args.trace:
         enable_tracing(True)
     torch.manual_seed(args.seed)  # main.py:70 — identical init on all ranks (plus a rank-0 broadcast)
-    train_set, test_set = get_datasets(args.data_root, args.synthetic, args.train_size, args.test_size)
+    train_set, test_set = get_datasets(args.data_root, args.synthetic, args.train_size, args.test_size,
+                                       dataset=getattr(args, "dataset", "cifar10"))
     sampler = ShardSampler(len(train_set), num_replicas=ctx.world, rank=ctx.rank, shuffle=True,
                            seed=args.sampler_seed, drop_last=False)
     train_loader = DeviceLoader(train_set, args.batch_size, ctx.device, sampler=sampler, train=True,
@@ -360,6 +364,8 @@ def run(ctx: DistContext, mode: str, args):
                 rec["scaling_efficiency"] = stats["images_per_sec_rank"] / base
             if res:
                 rec["test_loss"], rec["test_correct"] = res
+            if engine.num_classes != 10:
+                rec["dataset"], rec["num_classes"] = getattr(args, "dataset", "cifar10"), engine.num_classes
             if engine.label_smoothing:  # train_loss is then the smoothed loss, test_loss the plain one
                 rec["label_smoothing"] = engine.label_smoothing
             for k in ("mixup", "cutmix"):  # train_loss is then the pair-target loss of the mixed batches
