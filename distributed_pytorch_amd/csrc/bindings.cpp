@@ -1072,6 +1072,44 @@ void augment_mix(Tensor images, Tensor idx, Tensor labels, Tensor out, Tensor ta
       "augment_mix");
 }
 
+// Training augmentation, then RandAugment (n_ops ops from the table of cpu_ref.policy_params) and
+// Cutout (augment_policy.hip); out / target as augment.
+void augment_policy(Tensor images, Tensor idx, Tensor labels, Tensor out, OptT target, int64_t pad, int64_t seed,
+                    int64_t salt, std::vector<double> mean, std::vector<double> std_, Tensor table, int64_t n_ops,
+                    int64_t cutout, int64_t force_op) {
+  need(images, "images", at::kByte);
+  need(idx, "idx", at::kLong);
+  need(labels, "labels", at::kLong);
+  need(out, "out");
+  need(table, "table", at::kInt);
+  TORCH_CHECK(images.dim() == 4 && images.size(3) == 3, "augment_policy: images must be [N,H,W,3] uint8");
+  const int B = idx.numel(), Hs = images.size(1), Ws = images.size(2);
+  TORCH_CHECK(B >= 1, "augment_policy: empty batch");
+  TORCH_CHECK(out.numel() == (int64_t)B * Hs * Ws * 4, "augment_policy: out must be [B,H,W,4]");
+  TORCH_CHECK(table.numel() == 72, "augment_policy: table must be the 72 int32 words of policy_params");
+  TORCH_CHECK((int64_t)Hs * Ws <= 4096, "augment_policy: images above 4096 pixels are not served");
+  TORCH_CHECK(0 <= n_ops && n_ops <= 4, "augment_policy: n_ops must be in 0..4");
+  TORCH_CHECK(0 <= cutout && cutout <= std::min(Hs, Ws), "augment_policy: cutout must be in 0..min(H, W)");
+  TORCH_CHECK(-1 <= force_op && force_op <= 13, "augment_policy: force_op must be -1 or an op id in 0..13");
+  TORCH_CHECK(pad >= 0, "augment_policy: pad must be >= 0");
+  float m[3], s[3];
+  for (int c = 0; c < 3; ++c) {
+    m[c] = (float)mean.at(c);
+    s[c] = (float)std_.at(c);
+  }
+  long long* tp = nullptr;
+  if (target.has_value() && target->defined()) {
+    need(*target, "target", at::kLong);
+    TORCH_CHECK(target->numel() == B, "augment_policy: target must be [B]");
+    tp = reinterpret_cast<long long*>(target->data_ptr<int64_t>());
+  }
+  chk(dpa_augment_policy(images.data_ptr<uint8_t>(), reinterpret_cast<const long long*>(idx.data_ptr<int64_t>()),
+                         reinterpret_cast<const long long*>(labels.data_ptr<int64_t>()), fp(out), tp,
+                         table.data_ptr<int>(), B, Hs, Ws, (int)pad, (unsigned long long)seed,
+                         (unsigned long long)salt, m, s, (int)n_ops, (int)cutout, (int)force_op, cur_stream()),
+      "augment_policy");
+}
+
 // ---------------- NHWC max-pool (generic path) ----------------
 void maxpool_check(const Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 4, name, " must be a contiguous 4-D GPU tensor");
@@ -1391,6 +1429,9 @@ PYBIND11_MODULE(_C, m) {
         py::arg("target"), py::arg("target2"), py::arg("lam_out"), py::arg("pad"), py::arg("seed"), py::arg("salt"),
         py::arg("mean"), py::arg("std"), py::arg("mode"), py::arg("lam"), py::arg("y0") = 0, py::arg("y1") = 0,
         py::arg("x0") = 0, py::arg("x1") = 0);
+  m.def("augment_policy", &augment_policy, py::arg("images"), py::arg("idx"), py::arg("labels"), py::arg("out"),
+        py::arg("target"), py::arg("pad"), py::arg("seed"), py::arg("salt"), py::arg("mean"), py::arg("std"),
+        py::arg("table"), py::arg("n_ops"), py::arg("cutout"), py::arg("force_op") = -1);
   m.def("maxpool_fwd", &maxpool_fwd, py::arg("x"), py::arg("y"), py::arg("arg"), py::arg("k"), py::arg("s"),
         py::arg("p"), py::arg("scale") = py::none(), py::arg("shift") = py::none());
   m.def("maxpool_bwd", &maxpool_bwd);

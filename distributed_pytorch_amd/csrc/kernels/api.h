@@ -21,6 +21,15 @@ int dpa_augment_mix(const unsigned char* img, const long long* idx, const long l
                     long long* target, long long* target2, float* lam_out, int mode, float lam, int y0, int y1,
                     int x0, int x1, int B, int Hs, int Ws, int pad, unsigned long long seed, unsigned long long salt,
                     const float* mean, const float* std, hipStream_t st);
+// ---- augment_policy.hip ----
+// The training augmentation, then n_ops (0..4) RandAugment ops drawn per sample (force_op in 0..13
+// replaces every drawn op id, -1 = off) and a Cutout box of side cutout (0 = off, at most
+// min(Hs, Ws)), all in LDS.  table: the 72 int32 words of cpu_ref.policy_params on the device.
+// -2 before any launch: Hs * Ws > 4096 or an argument out of range.
+int dpa_augment_policy(const unsigned char* img, const long long* idx, const long long* labels, float* out,
+                       long long* target, const int* table, int B, int Hs, int Ws, int pad,
+                       unsigned long long seed, unsigned long long salt, const float* mean, const float* std,
+                       int n_ops, int cutout, int force_op, hipStream_t st);
 // ---- bn.hip ----
 // floats of partial workspace needed by fwd stats (2 per (block, channel)) / bwd (5 per ...)
 // (backward: rows of the fp32 or the bf16 geometry, whichever has more; the bf16 wide reduce of

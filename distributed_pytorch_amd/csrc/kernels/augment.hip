@@ -8,20 +8,9 @@
 // Per-sample crop offsets / flip come from a counter-based hash of (seed, sample index, salt),
 // so the stream is reproducible and independent of launch geometry.
 #include "api.h"
-#include "common.h"
+#include "augment_common.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-struct Norm {
-  float m[3], inv_s[3];
-};
 
 __global__ __launch_bounds__(256) void augment_kernel(const unsigned char* __restrict__ img,
                                                       const long long* __restrict__ idx,
@@ -73,34 +62,6 @@ struct Mix {
   int y0, y1, x0, x1;
 };
 
-struct Slot {
-  const unsigned char* im;
-  int dy, dx, flip;
-};
-
-__device__ __forceinline__ Slot slot_of(const unsigned char* img, const long long* idx, int s, int Hs, int Ws, int pad,
-                                        unsigned long long seed, unsigned long long salt) {
-  const unsigned long long h = mix64(seed ^ mix64(salt * 0x100000001B3ull + (unsigned long long)s));
-  const int span = 2 * pad + 1;
-  return Slot{img + (long)idx[s] * Hs * Ws * 3, (int)(h % span), (int)((h >> 16) % span), (int)((h >> 40) & 1)};
-}
-
-// augment_kernel's pixel: crop, flip, scale, normalise.  Contraction is off so that the value is the
-// separately rounded product / difference / product whatever surrounds the call (CutMix is bitwise).
-__device__ __forceinline__ float4 slot_px(const Slot& s, int y, int x, int Hs, int Ws, int pad, const Norm& nm) {
-#pragma clang fp contract(off)
-  const int xs = s.flip ? (Ws - 1 - x) : x;  // flip applied after the crop
-  const int sy = y + s.dy - pad, sx = xs + s.dx - pad;
-  float r = 0.f, g = 0.f, bl = 0.f;
-  if ((unsigned)sy < (unsigned)Hs && (unsigned)sx < (unsigned)Ws) {
-    const unsigned char* q = s.im + ((long)sy * Ws + sx) * 3;
-    r = q[0] * (1.f / 255.f);
-    g = q[1] * (1.f / 255.f);
-    bl = q[2] * (1.f / 255.f);
-  }
-  return make_float4((r - nm.m[0]) * nm.inv_s[0], (g - nm.m[1]) * nm.inv_s[1], (bl - nm.m[2]) * nm.inv_s[2], 0.f);
-}
-
 __global__ __launch_bounds__(256) void augment_mix_kernel(const unsigned char* __restrict__ img,
                                                           const long long* __restrict__ idx,
                                                           const long long* __restrict__ labels,
@@ -140,11 +101,7 @@ extern "C" int dpa_augment_mix(const unsigned char* img, const long long* idx, c
   if (mode != 0 && mode != 1) return -2;
   if (!(lam >= 0.f && lam <= 1.f) || !target || !target2 || !lam_out) return -2;
   if (mode == 1 && (y0 < 0 || y1 > Hs || x0 < 0 || x1 > Ws)) return -2;
-  Norm nm;
-  for (int c = 0; c < 3; ++c) {
-    nm.m[c] = mean[c];
-    nm.inv_s[c] = 1.f / std[c];
-  }
+  const Norm nm = make_norm(mean, std);
   augment_mix_kernel<<<B, 256, 0, st>>>(img, idx, labels, out, target, target2, lam_out, Hs, Ws, pad, seed, salt, nm,
                                         Mix{mode, lam, y0, y1, x0, x1});
   return (int)hipGetLastError();
@@ -153,11 +110,7 @@ extern "C" int dpa_augment_mix(const unsigned char* img, const long long* idx, c
 extern "C" int dpa_augment(const unsigned char* img, const long long* idx, const long long* labels, float* out,
                            long long* target, int B, int Hs, int Ws, int pad, int train, unsigned long long seed,
                            unsigned long long salt, const float* mean, const float* std, hipStream_t st) {
-  Norm nm;
-  for (int c = 0; c < 3; ++c) {
-    nm.m[c] = mean[c];
-    nm.inv_s[c] = 1.f / std[c];
-  }
+  const Norm nm = make_norm(mean, std);
   augment_kernel<<<B, 256, 0, st>>>(img, idx, labels, out, target, Hs, Ws, pad, train, seed, salt, nm);
   return (int)hipGetLastError();
 }

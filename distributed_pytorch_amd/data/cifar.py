@@ -198,6 +198,27 @@ class ShardSampler:
         return self.num_samples
 
 
+def check_policy(randaugment, cutout, hs: int = 32, ws: int = 32):
+    """``randaugment`` (None, or N ops in 1..4 and a magnitude in 0..30) and ``cutout`` (a side in
+    0..min(hs, ws)) as ((N, M) or None, S); anything else raises ValueError."""
+    if randaugment is not None:
+        try:
+            n, m = randaugment
+            ok = int(n) == n and int(m) == m and 1 <= n <= 4 and 0 <= m <= 30
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"randaugment must be (N, M) with N in 1..4 and M in 0..30, got {randaugment!r}")
+        randaugment = (int(n), int(m))
+    if cutout is None:
+        cutout = 0
+    if int(cutout) != cutout or not 0 <= cutout <= min(hs, ws):
+        raise ValueError(f"cutout must be an integer in 0..{min(hs, ws)}, got {cutout!r}")
+    if (randaugment is not None or cutout) and hs * ws > 4096:
+        raise ValueError(f"randaugment / cutout serve images of at most 4096 pixels, got {hs} x {ws}")
+    return randaugment, int(cutout)
+
+
 class DeviceLoader:
     """Iterates (x [n,H,W,4] fp32 NHWC, target [n] int64) batches produced on-device.
 
@@ -210,11 +231,19 @@ class DeviceLoader:
     function of (seed, epoch, batch index), so resuming mid-epoch reproduces the stream with no new
     state.  Iteration still yields (x, target); ``loader.mix`` is the persistent pair
     (target2 int64 [batch_size], lam float32 [batch_size]) whose first m entries belong to the batch
-    last yielded (for ``VGGEngine.set_mix`` / ``head_ce``), or None when mixing is off."""
+    last yielded (for ``VGGEngine.set_mix`` / ``head_ce``), or None when mixing is off.
+
+    ``randaugment=(N, M)`` (N ops in 1..4 at magnitude M in 0..30) and ``cutout=S`` (a box of side S,
+    at most the image's shorter side), training only, not with ``mixup`` / ``cutmix``: every batch
+    runs the policy kernel (``augment_policy``) in place of the plain augmentation; the ops, their
+    signs and the box are drawn per sample from the augmentation's own hash, so they too are a
+    function of (seed, epoch, batch index, slot).  With both off the loader launches what it
+    launched before."""
 
     def __init__(self, dataset: ImageSet, batch_size: int, device, sampler: Optional[ShardSampler] = None,
                  train: bool = True, seed: int = 0, pad: int = 4, backend=None, drop_last: bool = False,
-                 mixup: float = 0.0, cutmix: float = 0.0):
+                 mixup: float = 0.0, cutmix: float = 0.0, randaugment: Optional[Tuple[int, int]] = None,
+                 cutout: int = 0):
         self.device = torch.device(device)
         self.ds = dataset.to(self.device)
         self.batch_size = batch_size
@@ -247,6 +276,16 @@ class DeviceLoader:
         if self.mixup > 0 or self.cutmix > 0:
             self.mix = (torch.zeros(batch_size, dtype=torch.int64, device=self.device),
                         torch.ones(batch_size, dtype=torch.float32, device=self.device))
+        self.randaugment, self.cutout = check_policy(randaugment, cutout, *self.ds.images.shape[1:3])
+        self.policy = None  # the kernel's parameter table, when either option is on
+        if self.randaugment is not None or self.cutout:
+            if self.mix is not None:
+                raise ValueError("randaugment / cutout cannot be combined with mixup / cutmix")
+            if not train:
+                raise ValueError("randaugment / cutout apply to training batches only")
+            from ..ops.cpu_ref import policy_params
+
+            self.policy = policy_params((self.randaugment or (0, 0))[1], *self.ds.images.shape[1:3]).to(self.device)
 
     def set_epoch(self, epoch: int):
         self.epoch = epoch
@@ -282,7 +321,10 @@ class DeviceLoader:
             if self.drop_last and m < self.batch_size:
                 break
             salt = (self.epoch * 1_000_003 + b) & 0x7FFFFFFFFFFF
-            if self.mix is None:
+            if self.policy is not None:
+                self.K.augment_policy(self.ds.images, bi, self.ds.labels, self.x[:m], self.t[:m], self.pad, self.seed,
+                                      salt, MEAN, STD, self.policy, (self.randaugment or (0, 0))[0], self.cutout)
+            elif self.mix is None:
                 self.K.augment(self.ds.images, bi, self.ds.labels, self.x[:m], self.t[:m], self.pad, self.train,
                                self.seed, salt, MEAN, STD)
             else:

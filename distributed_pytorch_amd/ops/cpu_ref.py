@@ -455,3 +455,157 @@ def augment_mix(images, idx, labels, out, target, target2, lam_out, pad, seed, s
     out.copy_(res.reshape(out.shape))
     target2.copy_(labels[idx.long()].flip(0))
     lam_out.fill_(lam)
+
+
+# ---------------------------------------------------------------- RandAugment + Cutout
+POLICY_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color",
+              "Contrast", "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize")
+POLICY_SIGNED = range(1, 10)  # the ops whose magnitude takes the drawn sign
+POLICY_MAX_PIXELS = 4096
+# table layout: ops 1..5, six Q16 coefficients (column A, B, T; row C, D, T) for each sign at
+# ((op - 1) * 2 + sign) * 6; ops 6..9, the Q8 factor for each sign at 60 + (op - 6) * 2 + sign;
+# 68 the Posterize mask, 69 the Solarize threshold
+_T_BLEND, _T_POST, _T_SOL, POLICY_TABLE_LEN = 60, 68, 69, 72
+
+
+def policy_params(magnitude, Hs, Ws):
+    """The int32 table of what a RandAugment magnitude (0..30, torchvision's 31 bins) fixes for
+    Hs x Ws images, evaluated in Python floats and rounded once; the device evaluates no formula.
+    Geometric ops are inverse maps about the image centre in doubled, centred coordinates
+    X = 2x - (Ws-1), Y = 2y - (Hs-1): source X = (A X + B Y + T) / 65536, likewise the row."""
+    if not (isinstance(magnitude, int) and 0 <= magnitude <= 30):
+        raise ValueError(f"RandAugment magnitude must be an integer in 0..30, got {magnitude!r}")
+    if Hs < 1 or Ws < 1 or Hs * Ws > POLICY_MAX_PIXELS:
+        raise ValueError(f"the policy kernel serves 1 <= Hs * Ws <= {POLICY_MAX_PIXELS}, got {Hs} x {Ws}")
+    m = magnitude / 30.0
+    q16 = lambda v: int(round(v * 65536.0))
+    one = 65536
+    tab = [0] * POLICY_TABLE_LEN
+    for sign in (0, 1):
+        sg = -1.0 if sign else 1.0
+        sh = q16(sg * 0.3 * m)
+        th = math.radians(sg * 30.0 * m)
+        co, si = q16(math.cos(th)), q16(math.sin(th))
+        geo = {
+            1: (one, sh, 0, 0, one, 0),                                           # ShearX
+            2: (one, 0, 0, sh, one, 0),                                           # ShearY
+            3: (one, 0, -q16(sg * 2.0 * (150.0 / 331.0) * Ws * m), 0, one, 0),     # TranslateX: content moves by +t
+            4: (one, 0, 0, 0, one, -q16(sg * 2.0 * (150.0 / 331.0) * Hs * m)),     # TranslateY
+            5: (co, si, 0, -si, co, 0),                                           # Rotate
+        }
+        for op, c in geo.items():
+            tab[((op - 1) * 2 + sign) * 6:((op - 1) * 2 + sign) * 6 + 6] = c
+        for op in (6, 7, 8, 9):
+            tab[_T_BLEND + (op - 6) * 2 + sign] = int(round(256.0 * (1.0 + sg * 0.9 * m)))
+    bits = 8 - int(magnitude / 7.5)
+    tab[_T_POST] = 255 & ~((1 << (8 - bits)) - 1)
+    tab[_T_SOL] = int(255 - 255 * magnitude / 30)
+    return torch.tensor(tab, dtype=torch.int32)
+
+
+def policy_draws(seed, salt, b, n_ops, cutout, Hs, Ws, force_op=-1):
+    """([(op id, sign)] * n_ops, Cutout box (y0, y1, x0, x1)) of sample slot b -- bit-identical to
+    the HIP kernel's draws; the box is empty when cutout is 0."""
+    h = _mix64((seed & _MASK) ^ _mix64((salt * 0x100000001B3 + b) & _MASK))
+    ops = []
+    for k in range(n_ops):
+        u = _mix64(h ^ (0xA5A5A5A5 + k))
+        ops.append((force_op if force_op >= 0 else u % 14, (u >> 32) & 1))
+    box = (0, 0, 0, 0)
+    if cutout > 0:
+        u = _mix64(h ^ 0xC0C0C0C0)
+        ty, tx = u % Hs - cutout // 2, (u >> 16) % Ws - cutout // 2
+        box = (max(ty, 0), min(ty + cutout, Hs), max(tx, 0), min(tx + cutout, Ws))
+    return ops, box
+
+
+def _grey(v):
+    return (19595 * v[..., 0] + 38470 * v[..., 1] + 7471 * v[..., 2] + 32768) >> 16
+
+
+def policy_op(v, op, sign, table):
+    """One policy op on an int64 image v [H, W, 3] with values 0..255 -> the same; integers only."""
+    Hs, Ws = v.shape[0], v.shape[1]
+    t = [int(x) for x in table]
+    if 1 <= op <= 5:
+        c = t[((op - 1) * 2 + sign) * 6:][:6]
+        Y, X = torch.meshgrid(2 * torch.arange(Hs) - (Hs - 1), 2 * torch.arange(Ws) - (Ws - 1), indexing="ij")
+        sx = (c[0] * X + c[1] * Y + c[2] + Ws * 65536) >> 17
+        sy = (c[3] * X + c[4] * Y + c[5] + Hs * 65536) >> 17
+        ok = (sx >= 0) & (sx < Ws) & (sy >= 0) & (sy < Hs)
+        return v[sy.clamp(0, Hs - 1), sx.clamp(0, Ws - 1)] * ok[..., None]
+    if 6 <= op <= 9:
+        f = t[_T_BLEND + (op - 6) * 2 + sign]
+        if op == 6:
+            deg = torch.zeros_like(v)
+        elif op == 7:
+            deg = _grey(v)[..., None].expand_as(v)
+        elif op == 8:
+            deg = torch.full_like(v, (int(_grey(v).sum()) + Hs * Ws // 2) // (Hs * Ws))
+        else:
+            deg = v.clone()
+            if Hs > 2 and Ws > 2:
+                box = sum(v[1 + j:Hs - 1 + j, 1 + i:Ws - 1 + i] for j in (-1, 0, 1) for i in (-1, 0, 1))
+                deg[1:-1, 1:-1] = (box + 4 * v[1:-1, 1:-1] + 6) // 13
+        return ((deg * (256 - f) + v * f + 128) >> 8).clamp(0, 255)
+    if op == 10:
+        return v & t[_T_POST]
+    if op == 11:
+        return torch.where(v >= t[_T_SOL], 255 - v, v)
+    if op == 12:
+        lo, hi = v.amin((0, 1)), v.amax((0, 1))
+        rng = (hi - lo).clamp_min(1)
+        return torch.where(hi > lo, (255 * (v - lo) + (hi - lo) // 2) // rng, v)
+    if op == 13:
+        out = v.clone()
+        for c in range(3):
+            hist = torch.bincount(v[..., c].reshape(-1), minlength=256)
+            step = int(Hs * Ws - hist[int(hist.nonzero().max())]) // 255
+            if step:
+                lut = ((step // 2 + hist.cumsum(0) - hist) // step).clamp_max(255)
+                out[..., c] = lut[v[..., c]]
+        return out
+    if op != 0:
+        raise ValueError(f"op id must be in 0..13, got {op}")
+    return v
+
+
+def augment_policy(images, idx, labels, out, target, pad, seed, salt, mean, std, table, n_ops, cutout, force_op=-1):
+    """The training ``augment`` (crop, flip; out-of-image pixels 0) kept in uint8, then ``n_ops``
+    RandAugment ops per sample drawn by ``policy_draws``, then scale + normalise, then 0.0 in all
+    four channels inside the sample's Cutout box (native: augment_policy.hip).  Returns the list of
+    each slot's draws."""
+    B = idx.numel()
+    Hs, Ws = images.shape[1], images.shape[2]
+    if Hs * Ws > POLICY_MAX_PIXELS:
+        raise ValueError(f"the policy kernel serves Hs * Ws <= {POLICY_MAX_PIXELS}, got {Hs} x {Ws}")
+    if not 0 <= n_ops <= 4:
+        raise ValueError(f"n_ops must be in 0..4, got {n_ops}")
+    if not 0 <= cutout <= min(Hs, Ws):
+        raise ValueError(f"cutout must be in 0..{min(Hs, Ws)}, got {cutout}")
+    if not -1 <= force_op <= 13:
+        raise ValueError(f"force_op must be -1 or an op id in 0..13, got {force_op}")
+    if table.numel() != POLICY_TABLE_LEN or table.dtype != torch.int32:
+        raise ValueError("table must be the int32 table of policy_params")
+    m = torch.tensor(mean, dtype=torch.float32)
+    inv = 1.0 / torch.tensor(std, dtype=torch.float32)
+    src = images[idx.long()].long()
+    res = torch.zeros(B, Hs, Ws, 4)
+    draws = []
+    for b in range(B):
+        dy, dx, flip = aug_params(seed, salt, b, pad)
+        padded = torch.zeros(Hs + 2 * pad, Ws + 2 * pad, 3, dtype=torch.int64)
+        padded[pad:pad + Hs, pad:pad + Ws] = src[b]
+        v = padded[dy:dy + Hs, dx:dx + Ws]
+        if flip:
+            v = v.flip(1)
+        ops, (y0, y1, x0, x1) = policy_draws(seed, salt, b, n_ops, cutout, Hs, Ws, force_op)
+        for op, sign in ops:
+            v = policy_op(v, op, sign, table)
+        res[b, :, :, :3] = (v.float() * (1.0 / 255.0) - m) * inv
+        res[b, y0:y1, x0:x1] = 0.0
+        draws.append((ops, (y0, y1, x0, x1)))
+    out.copy_(res.reshape(out.shape))
+    if target is not None:
+        target.copy_(labels[idx.long()])
+    return draws

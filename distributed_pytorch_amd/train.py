@@ -25,6 +25,7 @@ import torch
 
 from .accum import AccumulatedStep, updates_per_epoch, validate_args
 from .data import NUM_CLASSES, DeviceLoader, ShardSampler, get_datasets
+from .data.cifar import check_policy
 from .engine import VGGEngine
 from .graph_step import GraphedStep
 from .parallel import DistContext, env_dict, init_cli, init_env, init_single, make_sync
@@ -213,6 +214,13 @@ def add_common_args(ap: argparse.ArgumentParser):
     mx.add_argument("--cutmix", type=float, default=0.0, metavar="ALPHA",
                     help="CutMix of the training batches: one box per batch of area share ~(1 - Beta(ALPHA, ALPHA)) "
                          "pasted from the mirror slot, lambda = the exact area share kept (default: 0 = off)")
+    g.add_argument("--randaugment", default=None, metavar="N,M",
+                   help="RandAugment of the training images on the device: N ops (1..4) per sample drawn from "
+                        "torchvision's 14 at magnitude M (0..30), after the crop and flip; not with --mixup / "
+                        "--cutmix (default: off)")
+    g.add_argument("--cutout", type=int, default=0, metavar="S",
+                   help="Cutout: a box of side S (0..32) around a per-sample centre set to the dataset mean, "
+                        "after the normalisation; not with --mixup / --cutmix (default: 0 = off)")
     g.add_argument("--lr-schedule", default=None, choices=["constant", "poly", "cosine", "step"],
                    help="learning-rate decay after the warmup, per iteration over epochs x iterations-per-epoch "
                         "steps (schedule.py); the rate then lives on the device, so --graph follows it "
@@ -271,6 +279,21 @@ def add_common_args(ap: argparse.ArgumentParser):
     return ap
 
 
+def policy_args(args):
+    """``--randaugment N,M`` and ``--cutout S`` of the command line as ((N, M) or None, S), checked
+    (CIFAR's 32 x 32 images); touches no device."""
+    ra = getattr(args, "randaugment", None)
+    if isinstance(ra, str):
+        try:
+            ra = tuple(int(v) for v in ra.split(","))
+        except ValueError:
+            raise ValueError(f"--randaugment takes two integers N,M, got {ra!r}") from None
+    ra, cut = check_policy(ra, getattr(args, "cutout", 0))
+    if (ra is not None or cut) and (getattr(args, "mixup", 0.0) or getattr(args, "cutmix", 0.0)):
+        raise ValueError("--randaugment / --cutout cannot be combined with --mixup / --cutmix")
+    return ra, cut
+
+
 def resume(ctx: DistContext, engine: VGGEngine, mode: str, args, n_batches: int):
     """Load this rank's checkpoint (``--resume``) and check that every rank resumes from the same
     point; returns (start_epoch, start_batch).  Runs BEFORE the sync strategy's start-up broadcast,
@@ -309,6 +332,7 @@ def build_engine(args, device) -> VGGEngine:
 
 def run(ctx: DistContext, mode: str, args):
     A = validate_args(args)
+    randaugment, cutout = policy_args(args)
     if args.trace:
         enable_tracing(True)
     torch.manual_seed(args.seed)  # main.py:70 — identical init on all ranks (plus a rank-0 broadcast)
@@ -318,7 +342,7 @@ def run(ctx: DistContext, mode: str, args):
                            seed=args.sampler_seed, drop_last=False)
     train_loader = DeviceLoader(train_set, args.batch_size, ctx.device, sampler=sampler, train=True,
                                 seed=args.seed * 7919 + ctx.rank, mixup=getattr(args, "mixup", 0.0),
-                                cutmix=getattr(args, "cutmix", 0.0))
+                                cutmix=getattr(args, "cutmix", 0.0), randaugment=randaugment, cutout=cutout)
     test_loader = DeviceLoader(test_set, args.batch_size, ctx.device, sampler=None, train=False)
     engine = build_engine(args, ctx.device)
     engine.init_parameters(seed=args.seed)
@@ -371,6 +395,10 @@ def run(ctx: DistContext, mode: str, args):
             for k in ("mixup", "cutmix"):  # train_loss is then the pair-target loss of the mixed batches
                 if getattr(args, k, 0.0):
                     rec[k] = getattr(args, k)
+            if randaugment is not None:
+                rec["randaugment"] = list(randaugment)
+            if cutout:
+                rec["cutout"] = cutout
             if A > 1:  # one update per A iterations; the throughput figures stay per loader batch
                 rec["accum_steps"], rec["effective_batch"] = A, A * ctx.world * args.batch_size
             if engine.lr_spec is not None:  # the rate of the epoch's last step
@@ -407,6 +435,7 @@ def main_cli(mode: str, argv=None):
     add_common_args(ap)
     args = ap.parse_args(argv)
     validate_args(args)  # before anything touches a device
+    policy_args(args)
     rc = _maybe_profile(args, argv)
     if rc is not None:
         raise SystemExit(rc)
@@ -420,6 +449,7 @@ def main_env(mode: str = "ddp", argv=None):
     add_common_args(ap)
     args = ap.parse_args(argv)
     validate_args(args)  # before anything touches a device
+    policy_args(args)
     rc = _maybe_profile(args, argv)
     if rc is not None:
         raise SystemExit(rc)
@@ -434,6 +464,7 @@ def main_single(argv=None):
     add_common_args(ap)
     args = ap.parse_args(argv)
     validate_args(args)  # before anything touches a device
+    policy_args(args)
     rc = _maybe_profile(args, argv)
     if rc is not None:
         raise SystemExit(rc)
